@@ -7,6 +7,15 @@ torch.distributed.run with --master-addr 127.0.0.1.
     python bench.py --gpus 1 --steps 20 --warmup 5
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 \
         --master-addr 127.0.0.1 bench.py --gpus 8 --steps 20 --warmup 5
+
+A plain run sets up, warms up, times --steps iterations and prints one JSON
+line. --dump-outputs DIR additionally writes what the last timed iteration
+left behind (net outputs, updated parameters and their gradients) as
+DIR/<name>.npy so two builds can be compared array for array; that iteration
+then starts from the seeded initial weights, so the arrays do not depend on
+run-to-run rounding noise accumulated over the earlier steps. --full is
+reserved for measurements beyond the headline figure; there are none at
+present, so it changes nothing.
 """
 
 import argparse
@@ -26,6 +35,55 @@ DEFAULT_BATCH = {  # per-GPU batch, matching the reference's training configs
     "lenet": 64,
 }
 
+DUMP_BUDGET_BYTES = 32 << 20  # all .npy files together stay under this
+DUMP_SAMPLE_SEED = 20240
+
+
+def dump_outputs(solver, out_dir):
+    """Write the arrays the last solver iteration produced as float32 .npy:
+    out_<blob> (net outputs, i.e. the loss), param_<i>_<name> (weights
+    after the update) and grad_<i>_<name> (the gradients that update
+    consumed) -- what a caller of solver.step() is left holding.
+    main() starts that iteration from the seeded initial weights, so the
+    arrays are one full step (forward, backward, update) of those weights.
+    Arrays larger than an equal share of DUMP_BUDGET_BYTES are reduced to a
+    fixed, seeded sample of their elements (same indices every run)."""
+    import numpy as np
+
+    arrays = []
+    for name in sorted(solver.net.output_blob_names):
+        arrays.append((f"out_{name}", solver.net.blobs[name].data))
+    for i, ps in enumerate(solver.net.params):
+        if ps.owner != i:
+            continue
+        arrays.append((f"param_{i}_{ps.blob.name}", ps.blob.data))
+        if ps.blob.has_diff():
+            arrays.append((f"grad_{i}_{ps.blob.name}", ps.blob.diff))
+    cap = max(1, DUMP_BUDGET_BYTES // 4 // len(arrays))
+    os.makedirs(out_dir, exist_ok=True)
+    for k, (name, t) in enumerate(arrays):
+        flat = t.detach().reshape(-1)
+        if flat.numel() > cap:
+            g = torch.Generator().manual_seed(DUMP_SAMPLE_SEED + k)
+            idx = torch.randint(0, flat.numel(), (cap,), generator=g)
+            flat = flat[idx.sort().values.to(flat.device)]
+            arr = flat.to(torch.float32).cpu().numpy()
+        else:
+            arr = t.detach().to(torch.float32).cpu().numpy()
+        fname = "".join(c if c.isalnum() or c in "._-" else "_" for c in name)
+        np.save(os.path.join(out_dir, fname + ".npy"), arr)
+
+
+def rewind(solver, start_state):
+    """Put the owned parameters back to start_state and clear the momentum
+    history, in place (tensor identities, and so the captured graph and the
+    multi-tensor tables, stay valid)."""
+    owned = [ps for i, ps in enumerate(solver.net.params) if ps.owner == i]
+    for ps, w0 in zip(owned, start_state):
+        ps.blob.data.copy_(w0)
+    for h in solver.history.values():
+        h.zero_()
+
 
 def main():
     ap = argparse.ArgumentParser()
@@ -44,6 +102,13 @@ def main():
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp32"],
                     help="compute dtype (activations + GEMM inputs); "
                          "master weights and gradient accumulation stay fp32")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="after the timed steps, write the last step's "
+                         "outputs, updated parameters and gradients to "
+                         "DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run measurements beyond the headline figure "
+                         "(none at present)")
     args = ap.parse_args()
 
     import poseidon_amd as pa
@@ -81,6 +146,13 @@ def main():
         if os.environ.get("PS_GRAPH", "1") != "0":
             graphed = solver.enable_graph()
 
+    start_state = None
+    if args.dump_outputs:
+        assert args.steps >= 1, "--dump-outputs needs at least one timed step"
+        start_state = [ps.blob.data.clone()
+                       for i, ps in enumerate(solver.net.params)
+                       if ps.owner == i]
+
     def sync():
         if device == "cuda":
             torch.cuda.synchronize()
@@ -91,15 +163,34 @@ def main():
     graphed = bool(solver._use_graph and solver._graph is not None)
     sync()
     t0 = time.perf_counter()
-    solver.step(args.steps)
-    sync()
-    elapsed = time.perf_counter() - t0
+    if start_state is None:
+        solver.step(args.steps)
+        sync()
+        elapsed = time.perf_counter() - t0
+    else:
+        # Split-K atomics make every step's gradients differ in the last
+        # bits from run to run, and training amplifies that over the steps.
+        # So that the dumped arrays depend only on the seed, the last timed
+        # step starts from the seeded initial weights and zero momentum;
+        # the rewind itself is kept off the clock.
+        solver.step(args.steps - 1)
+        sync()
+        elapsed = time.perf_counter() - t0
+        rewind(solver, start_state)
+        sync()
+        t0 = time.perf_counter()
+        solver.step(1)
+        sync()
+        elapsed += time.perf_counter() - t0
 
     # MAX elapsed over ranks (staged through the device for nccl/RCCL)
     t = torch.tensor([elapsed], dtype=torch.float64)
     if solver.distributed:
         comm.allreduce_max(t)
     elapsed = float(t[0])
+
+    if args.dump_outputs and rank == 0:
+        dump_outputs(solver, args.dump_outputs)
 
     if rank == 0:
         images = batch * n_gpus * args.steps

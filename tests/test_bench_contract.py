@@ -30,3 +30,36 @@ def test_bench_json_contract():
     for key in ("model", "global_batch", "input", "parallelism"):
         assert key in cfg, key
     assert cfg["parallelism"] == "dp1"
+
+
+def test_bench_dump_outputs_repeatable(tmp_path):
+    """--dump-outputs writes float32 .npy arrays (loss, parameters,
+    gradients) within the size budget, and two runs with the same arguments
+    write the same files with the same shapes (bit-identical on CPU)."""
+    import numpy as np
+
+    def run(d):
+        out = subprocess.run(
+            [sys.executable, os.path.join(REPO, "bench.py"), "--model",
+             "lenet", "--steps", "2", "--warmup", "1", "--no-graph",
+             "--full", "--dump-outputs", str(d)],
+            cwd=REPO, capture_output=True, text=True, timeout=600)
+        assert out.returncode == 0, out.stderr[-2000:]
+        rec = json.loads([l for l in out.stdout.splitlines()
+                          if l.startswith("{")][-1])
+        assert rec["steps"] == 2 and rec["ms_per_step"] > 0
+        return {f: np.load(os.path.join(d, f)) for f in sorted(os.listdir(d))}
+
+    a, b = run(tmp_path / "a"), run(tmp_path / "b")
+    assert list(a) == list(b)
+    assert any(f.startswith("out_") for f in a)
+    assert any(f.startswith("param_") for f in a)
+    assert any(f.startswith("grad_") for f in a)
+    assert sum(v.nbytes for v in a.values()) <= 64 << 20
+    on_cpu = not __import__("torch").cuda.is_available()
+    for f in a:
+        assert a[f].dtype == np.float32, f
+        assert a[f].shape == b[f].shape, f
+        assert np.isfinite(a[f]).all(), f
+        if on_cpu:  # GPU atomics reorder sums, so only CPU runs are bitwise
+            assert np.array_equal(a[f], b[f]), f

@@ -394,7 +394,7 @@ def test_full_solver_protocol_gpu(tmp_path):
         w0 = solver.net.learnable_params[0].blob.data
         assert torch.isfinite(w0).all()
     finally:
-        pa.init(device="cpu")
+        pa.init(device="cpu", compute_dtype=torch.float32)
 
 
 def test_threshold_eltwise_contrastive_kernels():
@@ -485,6 +485,7 @@ def test_deferred_wgrad_unpack_matches_eager():
         results.append({i: ps.blob.data.clone().cpu()
                         for i, ps in enumerate(s.net.params)
                         if ps.owner == i})
+    pa.init(device="cpu")
     for i in results[0]:
         assert torch.allclose(results[0][i], results[1][i],
                               rtol=1e-5, atol=1e-6), f"param {i}"
@@ -544,6 +545,7 @@ def test_concat_fused_relu_bwd_matches_eager():
                         for i, ps in enumerate(s.net.params)
                         if ps.owner == i})
     os.environ.pop("PS_NO_CONCAT_MASK", None)
+    pa.init(device="cpu")
     for i in results[0]:
         assert torch.allclose(results[0][i], results[1][i],
                               rtol=1e-5, atol=1e-6), f"param {i}"
