@@ -513,10 +513,11 @@ class Net:
                 w = l.blobs[0].data
                 Co, Cig, kh, kw = w.shape
                 G = l.group
-                is_1x1 = (kh == 1 and kw == 1 and l.stride == (1, 1)
-                          and l.pad == (0, 0))
-                ldc = (kh * kw * Cig * G) if is_1x1 else                     ops.conv_colT_ld(G, Cig * G, kh, kw, 8)
-                wk = torch.zeros(Co, ldc // G, dtype=torch.bfloat16,
+                # the width conv2d_forward_ex plans for (it rejects another)
+                x_shape = self.bottoms[self.layers.index(l)][0].shape
+                wk_ld = ops.conv_plan(x_shape, w.shape, l.stride, l.pad, G,
+                                      bf16=True)["wk_ld"]
+                wk = torch.zeros(Co, wk_ld, dtype=torch.bfloat16,
                                  device=w.device)
                 wkT = torch.empty(G * kh * kw * Cig, Co // G,
                                   dtype=torch.bfloat16, device=w.device)

@@ -4,6 +4,7 @@
 // math_functions.cu elementwise set.
 
 #include "ps_common.h"
+#include "ps_mt.h"
 
 namespace ps {
 
@@ -326,18 +327,6 @@ static inline dim3 colsum_flat_grid(int64_t nvec) {
 // 4 B banded form re-read slabs per band: both measured ~3x SLOWER than
 // the launches they replaced). Flush via LDS atomics once per block,
 // then one global atomicAdd per column. Dynamic LDS = max C floats.
-struct ColsumDesc {
-  const void* dy;
-  float* db;
-  int64_t R;
-  int64_t rows_per;
-  int C;
-};
-struct ColsumChunk {
-  int t;
-  int64_t off;
-};
-
 template <typename T>
 __global__ void colsum_mt_k(const ColsumDesc* __restrict__ descs,
                             const ColsumChunk* __restrict__ chunks) {

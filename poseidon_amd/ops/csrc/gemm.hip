@@ -22,6 +22,7 @@
 // Replaces the reference's cuBLAS call sites (math_functions.cu:16-65,
 // conv_layer.cu:25-121, inner_product_layer.cu:18-63).
 
+#include <algorithm>
 #include <type_traits>
 
 #include "ps_common.h"
@@ -768,13 +769,13 @@ __device__ inline void tr_wait(bf16x8 (&a)[NA], bf16x8 (&b)[NB]) {
 }
 
 template <int BM2, int BN2, int WGM2, int WGN2, bool SPLITK,
-          bool GB2 = false, bool WS = false>
+          bool GB2 = false>
 __global__ __launch_bounds__(256)
 void gemm_tn_tr_kernel(const __bf16* __restrict__ A,
                        const __bf16* __restrict__ B, float* __restrict__ C,
                        int M, int N, int K, int64_t ldA, int64_t ldB,
                        int64_t ldC, float alpha, int kchunk,
-                       GatherDesc ga_b = {}, float* __restrict__ ws = nullptr) {
+                       GatherDesc ga_b = {}) {
   constexpr int FM2 = BM2 / WGM2 / 16, FN2 = BN2 / WGN2 / 16;
   static_assert(WGM2 * WGN2 == 4, "4 waves");
   __shared__ __attribute__((aligned(16))) __bf16 a_lds[2][64 * BM2];
@@ -902,12 +903,7 @@ void gemm_tn_tr_kernel(const __bf16* __restrict__ A,
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int row = m0 + wm + fm * 16 + (lane >> 4) * 4 + r;
-        if (WS)
-          // workspace split-K: plain stores into this split's slice (alpha
-          // applied by splitk_reduce_k) -- no atomic serialization across
-          // the sk blocks sharing an output tile, no pre-zeroed C needed
-          ws[(int64_t)bz * M * N + (int64_t)row * N + col] = acc[fm][fn][r];
-        else if (SPLITK)
+        if (SPLITK)
           atomicAdd(&C[(int64_t)row * ldC + col], alpha * acc[fm][fn][r]);
         else
           C[(int64_t)row * ldC + col] = alpha * acc[fm][fn][r];
@@ -915,17 +911,56 @@ void gemm_tn_tr_kernel(const __bf16* __restrict__ A,
     }
 }
 
-// eligibility + launch; returns false if the caller must use the generic
-// path. C must be zeroed by the caller when split-K fires (atomic adds).
-template <typename T, typename OUT>
-static void gemm_dispatch(const GemmArgs& g, hipStream_t s);
+// ---------------------------------------------------------------------------
+// planning: path choice and split-K policy for one GEMM, made once
+// (ps_gemm_plan) and executed as planned (ps_gemm_run)
+// ---------------------------------------------------------------------------
 
-// Shared eligibility + shape plan for the tr16 TN path (used by both the
-// launcher and the bindings' workspace-size probe so the two can never
-// disagree). Returns false if the generic path must run; fills the
-// interior [M0 x N0], tile (bm, bn) and split-K factor for that interior.
-static bool tn_tr_plan(const GemmArgs& g, int* pM0, int* pN0, int* pbm,
-                       int* pbn, int* psk, int* pkchunk) {
+// what the generic launchers run: the problem plus the plan's split-K
+struct GemmLaunch : GemmArgs {
+  float* ws;   // split-K partials (splitk * M * N floats) or null: atomic
+  int splitk;  // > 1 needs batch == 1
+};
+
+template <typename T, typename OUT>
+static void gemm_dispatch(const GemmLaunch& g, hipStream_t s);
+
+// Tile selection shared by the generic launcher (grid) and the split-K
+// plan. Cost model: MFMA time on the PADDED output plus LDS staging traffic
+// (each A panel is re-staged once per N-tile and vice versa). ALPHA ~= MACs
+// the matrix cores retire per element the memory system delivers (bf16:
+// ~1.25e15 MAC/s vs ~3.2e12 elem/s -> ~400).
+static void pick_gemm_tile(int M, int N, int* bm_out, int* bn_out) {
+  const int cand[6][2] = {{128, 128}, {128, 32}, {32, 128}, {64, 64},
+                          {128, 16},  {16, 128}};
+  const double ALPHA = 400.0;
+  double best = 0;
+  for (int i = 0; i < 6; ++i) {
+    int bm = cand[i][0], bn = cand[i][1];
+    int64_t tm = (M + bm - 1) / bm, tn = (N + bn - 1) / bn;
+    double flops = (double)(tm * bm) * (tn * bn) / ALPHA;  // (x K, common)
+    double staging = (double)tm * bm * tn + (double)tn * bn * tm;
+    double cost = flops + staging;
+    if (i == 0 || cost < best) {
+      best = cost;
+      *bm_out = bm;
+      *bn_out = bn;
+    }
+  }
+}
+
+// Atomic split-K adds into C, which the launcher zeroes as ONE contiguous
+// M*N block: only when nothing else lands in C and its rows are dense.
+static bool atomic_splitk_ok(const GemmArgs& g) {
+  return g.out_f32 && g.bias == nullptr && g.beta == 0.0f && !g.relu &&
+         g.batch == 1 && g.ldc == g.N;
+}
+
+// Eligibility + shape plan for the tr16 TN path. Returns false if the
+// generic path must run; fills the interior [M0 x N0] (edge strips go
+// through the generic kernel), tile (bm, bn) and split-K for the interior.
+static bool tn_tr_plan(const GemmArgs& g, GemmPlan* p) {
+  if (!g.in_bf16 || !g.out_f32) return false;
   if (g.a_klast || g.b_klast || g.gather_a) return false;
   if (g.bias || g.relu || g.beta != 0.0f || g.batch > 1) return false;
   if (g.K % 64) return false;
@@ -948,7 +983,7 @@ static bool tn_tr_plan(const GemmArgs& g, int* pM0, int* pN0, int* pbm,
   int64_t tiles = (int64_t)(M0 / bm) * (N0 / bn);
   if (tiles >= 1024) return false;
   int sk = 1, kchunk = g.K;
-  if (tiles < 384 && g.K >= 512) {
+  if (tiles < 384 && g.K >= 512 && atomic_splitk_ok(g)) {
     int want = (int)((512 + tiles - 1) / tiles);
     int maxsk = (g.K + 255) / 256;
     sk = want < maxsk ? want : maxsk;
@@ -961,79 +996,79 @@ static bool tn_tr_plan(const GemmArgs& g, int* pM0, int* pN0, int* pbm,
     if (M0 == bm && kchunk > kcap && g.K > kcap) kchunk = kcap;
     sk = (g.K + kchunk - 1) / kchunk;
   }
-  *pM0 = M0; *pN0 = N0; *pbm = bm; *pbn = bn; *psk = sk; *pkchunk = kchunk;
+  *p = {true, sk, 0, M0, N0, bm, bn, kchunk};
   return true;
 }
 
-static bool try_gemm_tn_tr(const GemmArgs& g, hipStream_t s) {
-  int M0, N0, bm, bn, sk, kchunk;
-  if (!tn_tr_plan(g, &M0, &N0, &bm, &bn, &sk, &kchunk)) return false;
-  if (M0 != g.M || N0 != g.N) {
-    // edge strips go through the generic kernel; the [M0 x N0] interior
-    // through the tr path. Strips: [0,M) x [N0,N) and [M0,M) x [0,N0).
-    GemmArgs gi = g;
-    gi.M = M0; gi.N = N0;
-    if (!try_gemm_tn_tr(gi, s)) return false;
-    if (N0 != g.N) {
-      GemmArgs gt = g;
-      gt.N = g.N - N0;
-      gt.B = (const void*)((const __bf16*)g.B + N0);
-      gt.C = (void*)((float*)g.C + N0);
-      gt.ws = nullptr; gt.splitk = 1;
-      gemm_dispatch<__bf16, float>(gt, s);
+// Generic path: split K when the output tile grid cannot fill 256 CUs but
+// K is deep (conv wgrad: M=Cout, N=Kcol, K=N*OH*OW up to ~800k). 2
+// blocks/CU resident -> ~512 workgroups fill the chip; split K until the
+// grid gets there (wgrad at 512x4608 is 144 tiles = 28% occupancy without).
+static void generic_plan(const GemmArgs& g, GemmPlan* p) {
+  *p = {false, 1, 0, 0, 0, 0, 0, 0};
+  int tbm, tbn;
+  pick_gemm_tile(g.M, g.N, &tbm, &tbn);
+  const int64_t tiles =
+      (int64_t)((g.M + tbm - 1) / tbm) * ((g.N + tbn - 1) / tbn);
+  if (atomic_splitk_ok(g) && tiles < 384 && g.K >= 512) {
+    // atomic split-K: no workspace, so split much deeper (chunk >= 256)
+    // -- the un-split grid leaves most of the 256 CUs idle
+    int sk = (int)std::min<int64_t>((512 + tiles - 1) / tiles,
+                                    (g.K + 255) / 256);
+    if (sk > 1) p->splitk = sk;
+  } else if (g.batch == 1 && tiles < 384 && g.K >= 4096) {
+    // workspace split-K + reduce; cap the f32 workspace at 256 MB
+    int sk = (int)std::min<int64_t>((512 + tiles - 1) / tiles,
+                                    (g.K + 2047) / 2048);
+    int64_t ws_elems = (int64_t)sk * g.M * g.N;
+    if (sk > 1 && ws_elems * 4 <= (256LL << 20)) {
+      p->splitk = sk;
+      p->ws_elems = ws_elems;
     }
-    if (M0 != g.M) {
-      GemmArgs gt = g;
-      gt.M = g.M - M0; gt.N = N0;
-      gt.A = (const void*)((const __bf16*)g.A + M0);
-      gt.C = (void*)((float*)g.C + (int64_t)M0 * g.ldc);
-      gt.ws = nullptr; gt.splitk = 1;
-      gemm_dispatch<__bf16, float>(gt, s);
-    }
-    return true;
   }
+}
+
+// Atomic split-K accumulates into C: zero it here, once, unless the caller
+// owns a buffer that the net-level zero_mt launch already zeroed this
+// iteration (GoogLeNet: ~57 fillBuffer launches/step eliminated).
+// atomic_splitk_ok guarantees C is one dense M*N block.
+static void zero_c_for_atomics(const GemmArgs& g, hipStream_t s) {
+  if (!g.c_prezeroed)
+    (void)hipMemsetAsync(g.C, 0, (size_t)g.M * g.N * sizeof(float), s);
+}
+
+static void run_gemm_tn_tr(const GemmArgs& g, const GemmPlan& p,
+                           hipStream_t s) {
+  const int M0 = p.M0, N0 = p.N0, bm = p.bm, bn = p.bn, sk = p.splitk;
+  const int kchunk = p.kchunk;
   int skz = sk;
   if (sk > 1) {
-    const int nby = g.M / bm;
+    const int nby = M0 / bm;
     while (((int64_t)nby * skz) & 7) ++skz;  // pad: enables L2 clustering
+    zero_c_for_atomics(g, s);
   }
-  dim3 grid(g.N / bn, g.M / bm, skz);
-  const bool use_ws = sk > 1 && g.ws != nullptr;
-  if (sk > 1 && !use_ws && !g.c_prezeroed)
-    (void)hipMemsetAsync(g.C, 0, (size_t)g.M * g.N * sizeof(float), s);
+  dim3 grid(N0 / bn, M0 / bm, skz);
   GatherDesc gb = g.gather_b ? *g.gather_b : GatherDesc{};
 #define PS_TR_LAUNCH(BM_, BN_, WGM_, WGN_)                                  \
   do {                                                                      \
     if (g.gather_b) {                                                       \
-      if (use_ws)                                                           \
-        gemm_tn_tr_kernel<BM_, BN_, WGM_, WGN_, true, true, true>           \
-            <<<grid, 256, 0, s>>>((const __bf16*)g.A, (const __bf16*)g.B,   \
-                                  (float*)g.C, g.M, g.N, g.K, g.lda,        \
-                                  g.ldb, g.ldc, g.alpha, kchunk, gb,        \
-                                  (float*)g.ws);                            \
-      else if (sk > 1)                                                      \
+      if (sk > 1)                                                           \
         gemm_tn_tr_kernel<BM_, BN_, WGM_, WGN_, true, true>                 \
             <<<grid, 256, 0, s>>>((const __bf16*)g.A, (const __bf16*)g.B,   \
-                                  (float*)g.C, g.M, g.N, g.K, g.lda,        \
+                                  (float*)g.C, M0, N0, g.K, g.lda,          \
                                   g.ldb, g.ldc, g.alpha, kchunk, gb);       \
       else                                                                  \
         gemm_tn_tr_kernel<BM_, BN_, WGM_, WGN_, false, true>                \
             <<<grid, 256, 0, s>>>((const __bf16*)g.A, (const __bf16*)g.B,   \
-                                  (float*)g.C, g.M, g.N, g.K, g.lda,        \
+                                  (float*)g.C, M0, N0, g.K, g.lda,          \
                                   g.ldb, g.ldc, g.alpha, kchunk, gb);       \
-    } else if (use_ws)                                                      \
-      gemm_tn_tr_kernel<BM_, BN_, WGM_, WGN_, true, false, true>            \
-          <<<grid, 256, 0, s>>>((const __bf16*)g.A, (const __bf16*)g.B,     \
-                                (float*)g.C, g.M, g.N, g.K, g.lda, g.ldb,   \
-                                g.ldc, g.alpha, kchunk, GatherDesc{},       \
-                                (float*)g.ws);                              \
-    else if (sk > 1)                                                        \
+    } else if (sk > 1)                                                      \
       gemm_tn_tr_kernel<BM_, BN_, WGM_, WGN_, true><<<grid, 256, 0, s>>>(   \
-          (const __bf16*)g.A, (const __bf16*)g.B, (float*)g.C, g.M, g.N,    \
+          (const __bf16*)g.A, (const __bf16*)g.B, (float*)g.C, M0, N0,      \
           g.K, g.lda, g.ldb, g.ldc, g.alpha, kchunk);                       \
     else                                                                    \
       gemm_tn_tr_kernel<BM_, BN_, WGM_, WGN_, false><<<grid, 256, 0, s>>>(  \
-          (const __bf16*)g.A, (const __bf16*)g.B, (float*)g.C, g.M, g.N,    \
+          (const __bf16*)g.A, (const __bf16*)g.B, (float*)g.C, M0, N0,      \
           g.K, g.lda, g.ldb, g.ldc, g.alpha, kchunk);                       \
   } while (0)
   if (bm == 16 && bn == 128) PS_TR_LAUNCH(16, 128, 1, 4);
@@ -1043,15 +1078,22 @@ static bool try_gemm_tn_tr(const GemmArgs& g, hipStream_t s) {
   else if (bn == 128) PS_TR_LAUNCH(64, 128, 2, 2);
   else PS_TR_LAUNCH(64, 64, 2, 2);
 #undef PS_TR_LAUNCH
-  if (use_ws) {
-    int64_t MN = (int64_t)g.M * g.N;
-    int64_t rb = cdiv64(MN, 256);
-    if (rb > 2048) rb = 2048;
-    splitk_reduce_k<float, false><<<dim3((unsigned)rb), 256, 0, s>>>(
-        (const float*)g.ws, (float*)g.C, nullptr, g.M, g.N, g.ldc, sk,
-        g.alpha, 0.0f, false);
+  // edge strips [0,M) x [N0,N) and [M0,M) x [0,N0): generic kernel, unsplit
+  // (plain stores over the zeroed C)
+  if (N0 != g.N) {
+    GemmLaunch gt = {g, nullptr, 1};
+    gt.N = g.N - N0;
+    gt.B = (const void*)((const __bf16*)g.B + N0);
+    gt.C = (void*)((float*)g.C + N0);
+    gemm_dispatch<__bf16, float>(gt, s);
   }
-  return true;
+  if (M0 != g.M) {
+    GemmLaunch gt = {g, nullptr, 1};
+    gt.M = g.M - M0; gt.N = N0;
+    gt.A = (const void*)((const __bf16*)g.A + M0);
+    gt.C = (void*)((float*)g.C + (int64_t)M0 * g.ldc);
+    gemm_dispatch<__bf16, float>(gt, s);
+  }
 }
 
 // ---------------------------------------------------------------------------
@@ -1060,7 +1102,7 @@ static bool try_gemm_tn_tr(const GemmArgs& g, hipStream_t s) {
 
 template <typename T, typename OUT, int BM, int BN, int WGM, int WGN,
           bool AK, bool BK_, bool HB, bool GA = false, bool GB = false>
-static void launch_tile(const GemmArgs& g, hipStream_t s) {
+static void launch_tile(const GemmLaunch& g, hipStream_t s) {
   GatherDesc da = GA ? *g.gather_a : GatherDesc{};
   GatherDesc db = GB ? *g.gather_b : GatherDesc{};
   const bool sk = g.splitk > 1;
@@ -1122,9 +1164,9 @@ static void launch_tile(const GemmArgs& g, hipStream_t s) {
 
 template <typename T, typename OUT, bool AK, bool BK_, bool HB,
           bool GA = false, bool GB = false>
-static void dispatch_tiles(const GemmArgs& g, hipStream_t s) {
+static void dispatch_tiles(const GemmLaunch& g, hipStream_t s) {
   int bm, bn;
-  ps_pick_gemm_tile(g.M, g.N, &bm, &bn);
+  pick_gemm_tile(g.M, g.N, &bm, &bn);
   if (bm == 128 && bn == 32)
     launch_tile<T, OUT, 128, 32, 4, 1, AK, BK_, HB, GA, GB>(g, s);
   else if (bm == 32 && bn == 128)
@@ -1140,7 +1182,7 @@ static void dispatch_tiles(const GemmArgs& g, hipStream_t s) {
 }
 
 template <typename T, typename OUT>
-static void gemm_dispatch(const GemmArgs& g, hipStream_t s) {
+static void gemm_dispatch(const GemmLaunch& g, hipStream_t s) {
   const bool hb = g.bias != nullptr;
   if (g.a_klast && g.b_klast) {
     if (g.gather_a) {
@@ -1167,25 +1209,20 @@ static void gemm_dispatch(const GemmArgs& g, hipStream_t s) {
 
 extern "C" {
 
-// Returns the f32 workspace element count the tr16 TN path wants for this
-// GEMM (sk * interior M0 * N0), or 0 when it would not split / not take
-// the tr path. Callers that provide g->ws of this size get plain-store
-// split-K + a reduce instead of a memset + atomicAdd accumulation.
-int64_t ps_gemm_tn_tr_ws_elems(const GemmArgs* g) {
-  int M0, N0, bm, bn, sk, kchunk;
-  if (!tn_tr_plan(*g, &M0, &N0, &bm, &bn, &sk, &kchunk)) return 0;
-  return sk > 1 ? (int64_t)sk * M0 * N0 : 0;
+// tr16 plan first (bf16 in, fp32 out only), else the generic plan
+void ps_gemm_plan(const GemmArgs* g, GemmPlan* plan) {
+  if (!tn_tr_plan(*g, plan)) generic_plan(*g, plan);
 }
 
-void ps_gemm_f32(const GemmArgs* g, hipStream_t s) {
-  gemm_dispatch<float, float>(*g, s);
-}
-void ps_gemm_bf16_f32out(const GemmArgs* g, hipStream_t s) {
-  if (try_gemm_tn_tr(*g, s)) return;
-  gemm_dispatch<__bf16, float>(*g, s);
-}
-void ps_gemm_bf16(const GemmArgs* g, hipStream_t s) {
-  gemm_dispatch<__bf16, __bf16>(*g, s);
+// ws: plan->ws_elems floats (null when the plan asks for none)
+void ps_gemm_run(const GemmArgs* g, const GemmPlan* plan, float* ws,
+                 hipStream_t s) {
+  if (plan->tr16) return run_gemm_tn_tr(*g, *plan, s);
+  GemmLaunch l = {*g, plan->ws_elems > 0 ? ws : nullptr, plan->splitk};
+  if (l.splitk > 1 && !l.ws) zero_c_for_atomics(*g, s);
+  if (!g->in_bf16) gemm_dispatch<float, float>(l, s);
+  else if (g->out_f32) gemm_dispatch<__bf16, float>(l, s);
+  else gemm_dispatch<__bf16, __bf16>(l, s);
 }
 
 }  // extern "C"

@@ -4,6 +4,7 @@
 // Params and history are fp32 master copies; float4-vectorized.
 
 #include "ps_common.h"
+#include "ps_mt.h"
 
 namespace ps {
 
@@ -74,23 +75,9 @@ __global__ void adagrad_update_k(float* w, const float* g, float* h,
 // and zero launches cost more than the math (128 sgd_update_k + 116 zero_
 // launches/iter in the profile). One launch covers every param via a
 // device-resident (tensor-descriptor, chunk) table built once at solver
-// setup -- shapes are static so the table never changes.
+// setup -- shapes are static so the table never changes. Table layouts:
+// ps_mt.h.
 // ---------------------------------------------------------------------------
-
-struct MTDesc {
-  float* w;
-  const float* g;
-  float* h;
-  int64_t n;
-  float lr_mult;
-  float wd;
-};
-struct MTChunk {
-  int t;
-  int64_t off;
-};
-
-#define MT_CHUNK 8192  // elements per workgroup: 256 threads x vec4 x 8 iters
 
 template <bool LRDEV>
 __global__ void sgd_mt_k(const MTDesc* __restrict__ descs,
@@ -124,22 +111,9 @@ __global__ void sgd_mt_k(const MTDesc* __restrict__ descs,
   }
 }
 
-struct MTZeroDesc {
-  float* p;
-  int64_t n;
-};
-
 // Multi-tensor conv weight repack: one launch refreshes EVERY conv's bf16
 // khwc shadow + per-group dgrad transpose from the fp32 masters
 // (GoogLeNet: 2 launches instead of 68 x ~5 us repack kernels per step).
-struct MTRepackDesc {
-  const float* src;  // fp32 master, NCHW [Co][Cig][kh][kw]
-  void* wk;          // bf16 [Co][ldk] khwc (pad cols pre-zeroed)
-  void* wkT;         // bf16 [G*Kg][Cog]
-  int64_t n;         // Co*Cig*kh*kw
-  int Co, Cig, kh, kw, G, ldk;
-};
-
 __global__ void repack_mt_k(const MTRepackDesc* __restrict__ descs,
                             const MTChunk* __restrict__ chunks) {
   const MTChunk ck = chunks[blockIdx.x];
@@ -185,13 +159,6 @@ __global__ void repack_mt_k(const MTRepackDesc* __restrict__ descs,
 // fp32 param diff, accumulating (beta=1). One launch covers every conv's
 // unpack at the end of backward (GoogLeNet: 57 weight_from_khwc launches
 // -> 1) -- single-GPU mode only; DWBP needs per-layer grads final.
-struct MTUnpackDesc {
-  const float* dwk;  // fp32 [Co][ldk] khwc
-  float* dw;         // fp32 NCHW [Co][Cig][kh][kw], accumulated into
-  int64_t n;         // Co*Cig*kh*kw
-  int Co, Cig, kh, kw, ldk;
-};
-
 __global__ void unpack_mt_k(const MTUnpackDesc* __restrict__ descs,
                             const MTChunk* __restrict__ chunks) {
   const MTChunk ck = chunks[blockIdx.x];
@@ -260,8 +227,6 @@ void ps_sgd_update_lrdev(float* w, const float* g, float* h, int64_t n,
 void ps_u64_inc(void* p, hipStream_t s) {
   u64_inc_k<<<1, 1, 0, s>>>((unsigned long long*)p);
 }
-
-int ps_mt_chunk_elts(void) { return MT_CHUNK; }
 
 void ps_sgd_mt(const void* descs, const void* chunks, int nchunks, float lr,
                float mom, const float* lr_dev, hipStream_t s) {

@@ -55,6 +55,16 @@ def set_implicit_threshold(bytes_: int) -> None:
         _ext().set_implicit_threshold(int(bytes_))
 
 
+DGRAD_FWD_THRESHOLD_DEFAULT = 128 << 20
+
+
+def set_dgrad_fwd_threshold(bytes_: int) -> None:
+    """dcolT size above which a stride-1 conv dgrad runs as a forward conv
+    of dy with rotated weights (no dcolT, no col2im)."""
+    if ext_available():
+        _ext().set_dgrad_fwd_threshold(int(bytes_))
+
+
 def ext_available() -> bool:
     try:
         _ext()
@@ -525,8 +535,12 @@ def sgd_mt_run(mt, lr: float, momentum: float, lr_dev=None) -> None:
                       lr_dev)
 
 
-def conv_colT_ld(G: int, C: int, kh: int, kw: int, vec: int) -> int:
-    return int(_ext().colT_ld(G, C, kh, kw, vec))
+def conv_plan(x_shape, w_shape, stride, pad, groups: int, bf16: bool) -> dict:
+    """The conv layout plan the bindings derive for this problem (column
+    stride ld_col, padded weight width wk_ld, implicit / dgrad-as-forward
+    choices, ...) under the current implicit-GEMM policy."""
+    return _ext().conv_plan(list(x_shape), list(w_shape), list(stride),
+                            list(pad), int(groups), bool(bf16))
 
 
 def repack_mt_prepare(masters, wks, wkTs, Gs):

@@ -174,7 +174,7 @@ def test_bf16_training_converges():
 ])
 def test_gemm_bf16_tn_tr16(M, N, K):
     """TN bf16->f32 shapes routed through the ds_read_b64_tr_b16 kernel
-    (gemm.hip try_gemm_tn_tr) vs the fp32 torch reference."""
+    (gemm.hip run_gemm_tn_tr) vs the fp32 torch reference."""
     from poseidon_amd.ops._backend import load
     ext = load()
     opA = rnd(M, K, seed=5) * 0.3

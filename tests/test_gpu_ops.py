@@ -131,6 +131,206 @@ def _run_conv_case(cfg):
     close(db, db_ref, rtol=5e-4, atol=5e-4, what="conv bgrad")
 
 
+@pytest.mark.parametrize("bf16", [False, True])
+@pytest.mark.parametrize("cfg", [
+    dict(C=16, Co=16, k=3, p=1, g=1),
+    dict(C=16, Co=16, k=3, p=0, g=1),   # rotated pad = k-1
+    dict(C=32, Co=32, k=5, p=2, g=2),
+    dict(C=8, Co=8, k=3, p=1, g=1),     # bf16: Cog % 8 != 0 -> col2im path
+])
+def test_conv_dgrad_as_forward(cfg, bf16):
+    """Stride-1 dgrad as a forward conv of dy with rotated weights: forced
+    by dropping its byte threshold to 0 (no regular test shape reaches the
+    128 MiB default)."""
+    from test_gpu_bf16 import close_bf16
+    C, Co, k, p, g = cfg["C"], cfg["Co"], cfg["k"], cfg["p"], cfg["g"]
+    hw = 9
+    ho = hw + 2 * p - k + 1
+    w = rnd(Co, C // g, k, k, seed=12, scale=0.2)
+    dy = rnd(2, Co, ho, ho, seed=14)
+    x_shape = (2, C, hw, hw)
+    ops.set_dgrad_fwd_threshold(0)
+    try:
+        if bf16:
+            wq = w.to(torch.bfloat16).float()
+            dyq = dy.to(torch.bfloat16).float()
+            dx_ref = ops.conv2d_backward_input(wq, dyq, x_shape, (1, 1),
+                                               (p, p), g)
+            dx = ops.conv2d_backward_input(w.to(DEV),
+                                           dy.to(DEV, torch.bfloat16),
+                                           x_shape, (1, 1), (p, p), g)
+            close_bf16(dx, dx_ref, what="dgrad-as-fwd bf16")
+        else:
+            dx_ref = ops.conv2d_backward_input(w, dy, x_shape, (1, 1),
+                                               (p, p), g)
+            dx = ops.conv2d_backward_input(w.to(DEV), dy.to(DEV), x_shape,
+                                           (1, 1), (p, p), g)
+            close(dx, dx_ref, what="dgrad-as-fwd f32")
+    finally:
+        ops.set_dgrad_fwd_threshold(ops.DGRAD_FWD_THRESHOLD_DEFAULT)
+
+
+# literal expectations from the plan's rules: ld_col = Kcol for the aliasing
+# 1x1 case or G != 1, else Kcol rounded up to 64; wk_ld = ld_col / G;
+# Kgw_implicit = Kg rounded up to 64; implicit-eligible = !1x1 and Cg % vec
+# == 0 (vec = 8 bf16 / 4 fp32)
+_PLAN_CASES = [
+    # AlexNet conv1
+    (dict(C=3, hw=35, k=11, s=4, p=0, G=1),
+     dict(Kg=363, Kcol=363, ld_col=384, wk_ld=384, kpad=True, is_1x1=False,
+          Kgw_implicit=384), {8: False, 4: False}),
+    # AlexNet conv2
+    (dict(C=96, hw=13, k=5, s=1, p=2, G=2),
+     dict(Cg=48, Kg=1200, Kcol=2400, ld_col=2400, wk_ld=1200, kpad=False,
+          is_1x1=False, Kgw_implicit=1216), {8: True, 4: True}),
+    # 1x1 alias
+    (dict(C=16, hw=9, k=1, s=1, p=0, G=1),
+     dict(Kg=16, Kcol=16, ld_col=16, wk_ld=16, kpad=False, is_1x1=True),
+     {8: False, 4: False}),
+    # 1x1 stride 2: not the alias case, so padded like any G == 1 conv
+    (dict(C=16, hw=9, k=1, s=2, p=0, G=1),
+     dict(Kg=16, Kcol=16, ld_col=64, wk_ld=64, kpad=True, is_1x1=False,
+          Kgw_implicit=64), {8: True, 4: True}),
+    (dict(C=8, hw=9, k=3, s=1, p=1, G=1),
+     dict(Kg=72, Kcol=72, ld_col=128, wk_ld=128, kpad=True, is_1x1=False,
+          Kgw_implicit=128), {8: True, 4: True}),
+    (dict(C=64, hw=9, k=3, s=1, p=1, G=1),
+     dict(Kg=576, Kcol=576, ld_col=576, wk_ld=576, kpad=False, is_1x1=False,
+          Kgw_implicit=576), {8: True, 4: True}),
+]
+
+
+@pytest.mark.parametrize("bf16", [True, False])
+@pytest.mark.parametrize("case", _PLAN_CASES)
+def test_conv_plan_values(case, bf16):
+    cfg, want, eligible = case
+    vec = 8 if bf16 else 4
+    Co = 16
+    args = ((2, cfg["C"], cfg["hw"], cfg["hw"]),
+            (Co, cfg["C"] // cfg["G"], cfg["k"], cfg["k"]),
+            (cfg["s"], cfg["s"]), (cfg["p"], cfg["p"]), cfg["G"], bf16)
+    plan = ops.conv_plan(*args)
+    ho = (cfg["hw"] + 2 * cfg["p"] - cfg["k"]) // cfg["s"] + 1
+    want = dict(want, vec=vec, Co=Co, Cog=Co // cfg["G"], Ho=ho, Wo=ho,
+                NP=2 * ho * ho,
+                implicit=False,       # default policy: these colT are tiny
+                dgrad_as_fwd=False)
+    for key, val in want.items():
+        assert plan[key] == val, f"{cfg} bf16={bf16}: {key}={plan[key]}"
+    # with implicit GEMM forced, the choice is the eligibility rule alone
+    ops.set_implicit_gemm(True)
+    try:
+        forced = ops.conv_plan(*args)
+    finally:
+        ops.set_implicit_gemm(False)
+    assert forced["implicit"] == eligible[vec], f"{cfg} bf16={bf16}"
+    for key in ("ld_col", "wk_ld", "kpad"):
+        assert forced[key] == plan[key]
+
+
+def test_net_repack_cache_is_consumed():
+    """The persistent wk buffers Net sizes for the multi-tensor repack have
+    exactly the width the conv binding plans for (a mismatch is an error in
+    the binding, not a silent per-layer repack), and the net computes what
+    the CPU net computes."""
+    from test_gpu_bf16 import close_bf16
+    from poseidon_amd.core.net import Net, TRAIN
+    from poseidon_amd.proto import parse_text
+
+    def net_param():
+        return parse_text("NetParameter", """
+            name: "repack4"
+            layers { name: "data" type: DUMMY_DATA top: "data" top: "label"
+                     dummy_data_param { num: 2 channels: 3 height: 11
+                         width: 11 num: 2 channels: 1 height: 1 width: 1
+                         data_filler { type: "gaussian" std: 1.0 }
+                         data_filler { type: "constant" } } }
+            layers { name: "c1" type: CONVOLUTION bottom: "data" top: "c1"
+                     convolution_param { num_output: 8 kernel_size: 3 pad: 1
+                         weight_filler { type: "xavier" }
+                         bias_filler { type: "constant" value: 0.1 } } }
+            layers { name: "c2" type: CONVOLUTION bottom: "c1" top: "c2"
+                     convolution_param { num_output: 16 kernel_size: 1
+                         weight_filler { type: "xavier" } } }
+            layers { name: "c3" type: CONVOLUTION bottom: "c2" top: "c3"
+                     convolution_param { num_output: 16 kernel_size: 3 pad: 1
+                         group: 2 weight_filler { type: "xavier" } } }
+            layers { name: "c4" type: CONVOLUTION bottom: "c3" top: "c4"
+                     convolution_param { num_output: 8 kernel_size: 1
+                         stride: 2 weight_filler { type: "xavier" } } }
+            layers { name: "ip" type: INNER_PRODUCT bottom: "c4" top: "ip"
+                     inner_product_param { num_output: 4
+                         weight_filler { type: "xavier" } } }
+            layers { name: "loss" type: SOFTMAX_LOSS bottom: "ip"
+                     bottom: "label" top: "loss" }
+        """)
+
+    def bf16_exact(t):  # same operands on both sides: no input rounding
+        return t.to(torch.bfloat16).float()
+
+    def run(net, data, labels, dtype):
+        dev = pa.ctx().torch_device
+        net.blobs["data"].data = data.to(dev, dtype)
+        net.blobs["label"].data = labels.to(dev)
+        net.layers[0]._filled = True
+        net.layers[0].refill = [False, False]
+        loss = net.forward()
+        net.zero_param_diffs()
+        net.backward()
+        return loss
+
+    g = torch.Generator().manual_seed(21)
+    data = bf16_exact(torch.randn(2, 3, 11, 11, generator=g))
+    labels = torch.tensor([1.0, 3.0]).view(2, 1, 1, 1)
+    pa.init(device="cpu", seed=31)
+    ref = Net(net_param(), phase=TRAIN, verbose=False)
+    for ps_ in ref.learnable_params:
+        ps_.blob.data.copy_(bf16_exact(ps_.blob.data))
+    loss_ref = run(ref, data, labels, torch.float32)
+
+    pa.init(device="cuda", seed=31, compute_dtype=torch.bfloat16)
+    try:
+        net = Net(net_param(), phase=TRAIN, verbose=False)
+        for ps_, rs in zip(net.learnable_params, ref.learnable_params):
+            ps_.blob.data.copy_(rs.blob.data)
+        loss = run(net, data, labels, torch.bfloat16)
+        torch.cuda.synchronize()
+        convs = [(i, l) for i, l in enumerate(net.layers)
+                 if l.type_name == "CONVOLUTION"]
+        assert len(convs) == 4
+        for (i, l), wk_ld in zip(convs, [64, 8, 72, 64]):
+            plan = ops.conv_plan(net.bottoms[i][0].shape,
+                                 l.blobs[0].data.shape, l.stride, l.pad,
+                                 l.group, True)
+            assert plan["wk_ld"] == wk_ld, l.name
+            assert l._wk_cache[0].shape[1] == wk_ld, l.name
+        close_bf16(torch.tensor(loss), torch.tensor(loss_ref), what="loss")
+        for ps_, rs in zip(net.learnable_params, ref.learnable_params):
+            close_bf16(ps_.blob.diff, rs.blob.diff, what=ps_.blob.name)
+    finally:
+        pa.init(device="cpu", compute_dtype=torch.float32)
+
+
+def test_conv_forward_rejects_wrong_wk_width():
+    """Pre-repacked weights of the compute dtype but not the planned width
+    are an error, not a silent per-layer repack."""
+    x = rnd(2, 3, 9, 9, seed=11).to(DEV)
+    w = rnd(8, 3, 3, 3, seed=12, scale=0.2).to(DEV)
+    wk_ld = ops.conv_plan(x.shape, w.shape, (1, 1), (1, 1), 1, False)["wk_ld"]
+    assert wk_ld == 64
+    wkT = torch.empty(27, 8, device=DEV)
+    with pytest.raises(RuntimeError, match="wk_ld"):
+        ops.conv2d_forward_ex(x, w, None, (1, 1), (1, 1), 1,
+                              cached=(torch.zeros(8, 27, device=DEV), wkT))
+    # bf16 shadows under fp32 compute keep the per-layer repack fallback
+    y_ref, _ = ops.conv2d_forward_ex(x.cpu(), w.cpu(), None, (1, 1), (1, 1), 1)
+    y, _ = ops.conv2d_forward_ex(
+        x, w, None, (1, 1), (1, 1), 1,
+        cached=(torch.zeros(8, 27, device=DEV, dtype=torch.bfloat16),
+                wkT.to(torch.bfloat16)))
+    close(y, y_ref, what="conv fwd, shadows of another dtype")
+
+
 # ---------------------------------------------------------------------------
 # Pooling / LRN
 # ---------------------------------------------------------------------------
