@@ -456,14 +456,17 @@ class Net:
                  if getattr(l, "_unpack_pending", False)]
         if not convs:
             return
-        key = [(id(l._dwk_cache), id(l.blobs[0].diff)) for l in convs]
+        key = [(id(l._dwk_cache), id(l.blobs[0].diff), l._dwk_layout)
+               for l in convs]
         if self._unpack_mt is None or self._unpack_mt[1] != key:
             self._unpack_mt = (ops.unpack_mt_prepare(
                 [l._dwk_cache for l in convs],
                 [l.blobs[0].diff for l in convs],
                 [l.blobs[0].data.shape[1] for l in convs],
                 [l.blobs[0].data.shape[2] for l in convs],
-                [l.blobs[0].data.shape[3] for l in convs]), key)
+                [l.blobs[0].data.shape[3] for l in convs],
+                [l._dwk_layout[0] for l in convs],
+                [l._dwk_layout[1] for l in convs]), key)
         ops.unpack_mt_run(self._unpack_mt[0])
         for l in convs:
             l._unpack_pending = False
@@ -506,17 +509,26 @@ class Net:
                and l.blobs[0].data.dtype == torch.float32]
         if not convs and not ips:
             return
+        # the policy epoch: a conv-policy setter may have changed a plan's
+        # khwc layout since the shadows were sized
         key = [id(l.blobs[0].data) for l in convs + ips]
+        key.append(ops.conv_policy_epoch())
         if self._repack_mt is None or self._repack_key != key:
-            masters, wks, wkTs, Gs = [], [], [], []
+            masters, wks, wkTs, Gs, kw_lds, c_lds = [], [], [], [], [], []
             for l in convs:
                 w = l.blobs[0].data
                 Co, Cig, kh, kw = w.shape
                 G = l.group
-                # the width conv2d_forward_ex plans for (it rejects another)
+                # the width and khwc layout conv2d_forward_ex plans for (it
+                # rejects another width). Columns the repack never writes
+                # (pad columns, a packed first layer's unused channel slots
+                # and phantom taps) are zeroed here, once.
                 x_shape = self.bottoms[self.layers.index(l)][0].shape
-                wk_ld = ops.conv_plan(x_shape, w.shape, l.stride, l.pad, G,
-                                      bf16=True)["wk_ld"]
+                plan = ops.conv_plan(x_shape, w.shape, l.stride, l.pad, G,
+                                     bf16=True)
+                wk_ld = plan["wk_ld"]
+                kw_lds.append(plan["kw_ld"])
+                c_lds.append(plan["c_ld"])
                 wk = torch.zeros(Co, wk_ld, dtype=torch.bfloat16,
                                  device=w.device)
                 wkT = torch.empty(G * kh * kw * Cig, Co // G,
@@ -539,7 +551,10 @@ class Net:
                 wkTs.append(torch.empty(0, dtype=torch.bfloat16,
                                         device=w.device))
                 Gs.append(1)
-            self._repack_mt = ops.repack_mt_prepare(masters, wks, wkTs, Gs)
+                kw_lds.append(1)
+                c_lds.append(l.K)
+            self._repack_mt = ops.repack_mt_prepare(masters, wks, wkTs, Gs,
+                                                    kw_lds, c_lds)
             self._repack_key = key
         ops.repack_mt_run(self._repack_mt)
 

@@ -49,6 +49,8 @@ class ConvolutionLayer(Layer):
                                 # net-level multi-tensor repack each step
         self._dwk_cache = None  # persistent khwc wgrad scratch (zeroed per
                                 # iter by the net zero table)
+        self._dwk_packed = None  # whether that scratch is in packed layout
+        self._dwk_layout = None  # its (kw_ld, c_ld), ops.khwc_layout
         self._unpack_pending = False  # deferred wgrad unpack flag
         self._dx_cache = {}     # persistent dgrad outputs (stable dy
                                 # identities for downstream batching)
@@ -127,6 +129,14 @@ class ConvolutionLayer(Layer):
             if defer_db:
                 # bias grad joins the ONE net-level colsum_mt launch
                 self._pending_colsum = (dy, db)
+            if dwk is not None:
+                # the scratch has the layout the FORWARD chose (a 4-D cache
+                # slot is the packed input): the net-level unpack reads it
+                packed = colT is not None and colT.dim() == 4
+                if packed != self._dwk_packed or self._dwk_layout is None:
+                    self._dwk_packed = packed
+                    self._dwk_layout = ops.khwc_layout(
+                        w.shape[1], w.shape[3], packed)
             if defer:
                 if dwk.data_ptr() != self._dwk_cache.data_ptr():
                     raise RuntimeError(

@@ -18,6 +18,7 @@
 #include <algorithm>
 #include <atomic>
 #include <cmath>
+#include <cstdlib>
 #include <utility>
 
 #include "ps_api.h"
@@ -119,8 +120,18 @@ std::atomic<int64_t> g_implicit_thresh{192LL << 20};
 // dcolT it eliminates exceeds this (no dcolT round-trip -- up to 2 GB for
 // VGG conv1_2 -- and no col2im)
 std::atomic<int64_t> g_dgrad_fwd_thresh{128LL << 20};
+// Packed small-channel first layers (ps_conv_plan.h, PS_PK_SLOTS): G==1,
+// C<=4, even-sw bf16 convs run forward and wgrad through the gather GEMMs
+// from a pair-packed copy of x -- no colT, no im2col. Default OFF: measured
+// on AlexNet conv1 (docs/performance.md item 20) the im2col and layout
+// copies it removes (0.34 ms) cost less than the gather GEMMs lose to the
+// 1.5x longer packed K (wgrad 316 -> 634 us, forward 303 -> 382 us);
+// GoogLeNet's 7x7 conv1 gains 1.3% with it on. PS_PACKED_CONV=1 turns it on
+// at import.
+std::atomic<bool> g_packed_conv{false};
 
 void set_implicit_gemm(bool on) { g_implicit_gemm.store(on); }
+void set_packed_conv(bool on) { g_packed_conv.store(on); }
 void set_implicit_threshold(int64_t bytes) { g_implicit_thresh.store(bytes); }
 void set_dgrad_fwd_threshold(int64_t bytes) { g_dgrad_fwd_thresh.store(bytes); }
 
@@ -274,12 +285,19 @@ Tensor gemm_at_b(const Tensor& a, const Tensor& b) {
 // comes from the ConvPlan (ps_conv_plan.h).
 // ---------------------------------------------------------------------------
 
+// packed: PS_PACKED_AUTO asks the global policy; the wgrad passes what its
+// forward actually did (read off the cache slot) instead
+enum { PS_PACKED_OFF = 0, PS_PACKED_ON = 1, PS_PACKED_AUTO = -1 };
+
 ConvPlan conv_plan_for(at::IntArrayRef x_shape, int Co, int kh, int kw,
-                       int sh, int sw, int ph, int pw, int G, bool bf16) {
+                       int sh, int sw, int ph, int pw, int G, bool bf16,
+                       int packed = PS_PACKED_AUTO) {
   TORCH_CHECK(x_shape.size() == 4 && G > 0 && x_shape[1] % G == 0 &&
               Co % G == 0, "conv channel/group mismatch");
-  const ConvPolicy policy = {g_implicit_gemm.load(), g_implicit_thresh.load(),
-                             g_dgrad_fwd_thresh.load()};
+  const ConvPolicy policy = {
+      g_implicit_gemm.load(), g_implicit_thresh.load(),
+      g_dgrad_fwd_thresh.load(),
+      packed == PS_PACKED_AUTO ? g_packed_conv.load() : packed == PS_PACKED_ON};
   return ps_conv_plan((int)x_shape[0], (int)x_shape[1], (int)x_shape[2],
                       (int)x_shape[3], Co, kh, kw, sh, sw, ph, pw, G,
                       bf16 ? 2 : 4, policy);
@@ -304,7 +322,18 @@ py::dict conv_plan(std::vector<int64_t> x_shape, std::vector<int64_t> w_shape,
   d["is_1x1"] = p.is_1x1; d["ld_col"] = p.ld_col; d["wk_ld"] = p.wk_ld;
   d["kpad"] = p.kpad; d["implicit"] = p.implicit;
   d["Kgw_implicit"] = p.Kgw_implicit; d["dgrad_as_fwd"] = p.dgrad_as_fwd;
+  d["packed"] = p.packed; d["pk_W"] = p.pk_W; d["pk_kw"] = p.pk_kw;
+  d["pk_Kg"] = p.pk_Kg; d["kw_ld"] = p.kw_ld; d["c_ld"] = p.c_ld;
+  // width of the khwc wgrad scratch
+  d["Kgw"] = p.implicit ? p.Kgw_implicit : p.wk_ld;
   return d;
+}
+
+// (kw_ld, c_ld) of a conv's khwc rows, packed or plain
+std::vector<int64_t> khwc_layout(int64_t Cg, int64_t kw, bool packed) {
+  int kw_ld, c_ld;
+  ps_khwc_layout((int)kw, (int)Cg, packed, &kw_ld, &c_ld);
+  return {kw_ld, c_ld};
 }
 
 // weights [Co,Cig,kh,kw] fp32 -> khwc [Co, kh*kw*Cig] in compute dtype
@@ -327,13 +356,16 @@ std::vector<Tensor> conv2d_forward_ex(const Tensor& x, const Tensor& w,
                                       const c10::optional<Tensor>& wkT_cached) {
   check_float_like(x, "x");
   const bool bf16 = is_bf16(x);
-  auto x_cl = cl4(x);
-  TORCH_CHECK(w.size(1) * G == x_cl.size(1), "conv channel/group mismatch");
-  const ConvPlan p = conv_plan_for(x_cl.sizes(), (int)w.size(0),
+  TORCH_CHECK(x.dim() == 4 && w.size(1) * G == x.size(1),
+              "conv channel/group mismatch");
+  const ConvPlan p = conv_plan_for(x.sizes(), (int)w.size(0),
                                    (int)w.size(2), (int)w.size(3), sh, sw, ph,
                                    pw, G, bf16);
   const ConvGeom& g = p.g;
   const int Co = p.Co, Cog = p.Cog;
+  // only the 1x1 alias and the implicit gather want x channels-last as a
+  // whole; the other paths read it through its own strides (below)
+  Tensor x_cl = (p.is_1x1 || p.implicit) ? cl4(x) : Tensor();
 
   // fused repack: one kernel writes both the khwc fwd operand and the
   // per-group transpose the dgrad GEMM wants (cached by the layer). When
@@ -356,20 +388,35 @@ std::vector<Tensor> conv2d_forward_ex(const Tensor& x, const Tensor& w,
                 : at::empty({Co, (int64_t)p.wk_ld}, wkopts);
     wkT = at::empty({(int64_t)p.Kcol, (int64_t)Cog}, wkopts);
     PS_CALL_W(weight_to_khwc_both, bf16, wc.data_ptr<float>(), P(wk), P(wkT),
-            Co, p.Cg, g.kh, g.kw, G, p.wk_ld, stream());
+            Co, p.Cg, g.kh, g.kw, G, p.wk_ld, p.kw_ld, p.c_ld, stream());
   }
 
+  // the cache slot: colT, the empty 1-D implicit sentinel, or -- 4-D -- the
+  // packed xp, which the wgrad gathers from (it never touches x again)
   Tensor colT;
-  if (p.is_1x1) {
+  if (p.packed) {
+    colT = at::empty({g.N, g.H, (int64_t)p.pk_W, PS_PK_C}, x.options());
+    ps_pack_pairs_bf16(x.data_ptr(), colT.data_ptr(), g.N, g.C, g.H, g.W,
+                       p.pk_W, g.pw, x.stride(0), x.stride(1), x.stride(2),
+                       x.stride(3), stream());
+  } else if (p.is_1x1) {
     colT = rows2d(x_cl);  // alias: x rows ARE the col rows
   } else if (!p.implicit) {
     colT = at::empty({p.NP, (int64_t)p.ld_col}, x.options());
-    PS_CALL(im2col_nhwc, bf16, P(x_cl), P(colT), &g, p.ld_col, stream());
-    // pad columns (ld_col > Kcol) must be zero for the GEMMs; only the
-    // rowstage kernel writes them itself -- zero unconditionally (cheap,
-    // <= 63 columns)
-    if (p.kpad)
-      PS_CALL(zero_cols, bf16, P(colT), p.NP, p.ld_col, p.Kcol, stream());
+    // the rowstage im2col of a small-channel first layer reads the (NCHW)
+    // data blob as it is; every other shape wants NHWC, which activations
+    // already are
+    const bool staged = PS_CALL(im2col_rowstage, bf16, P(x), P(colT), &g,
+                                p.ld_col, x.stride(0), x.stride(1),
+                                x.stride(2), x.stride(3), stream());
+    if (!staged) {
+      const Tensor xc = cl4(x);
+      PS_CALL(im2col_nhwc, bf16, P(xc), P(colT), &g, p.ld_col, stream());
+      // pad columns (ld_col > Kcol) must be zero for the GEMMs; only the
+      // rowstage kernel writes them itself
+      if (p.kpad)
+        PS_CALL(zero_cols, bf16, P(colT), p.NP, p.ld_col, p.Kcol, stream());
+    }
   }
 
   Tensor y = empty_cl({g.N, Co, g.Ho, g.Wo}, x.options());
@@ -383,18 +430,19 @@ std::vector<Tensor> conv2d_forward_ex(const Tensor& x, const Tensor& w,
   // GEMM runs over the padded K too (gather k >= kg_max reads the zero
   // page, wk pad cols are zero)
   const int Kgl = p.wk_ld;
+  const bool gather = p.implicit || p.packed;
+  const Tensor& xg = p.packed ? colT : x_cl;  // what the gather reads
   for (int grp = 0; grp < G; ++grp) {
     GatherDesc ga{};
-    if (p.implicit)
-      ga = ps_gather_desc(p, PS_GATHER_FWD, x_cl.data_ptr(), zero_page(x_cl),
-                          grp);
-    run_gemm(p.implicit ? x_cl : colT, wk, y, bp ? bp + grp * Cog : nullptr,
+    if (gather)
+      ga = ps_gather_desc(p, PS_GATHER_FWD, xg.data_ptr(), zero_page(xg), grp);
+    run_gemm(gather ? xg : colT, wk, y, bp ? bp + grp * Cog : nullptr,
              (int)p.NP, Cog, Kgl,
-             /*lda=*/p.implicit ? Kgl : p.ld_col, /*ldb=*/Kgl, /*ldc=*/Co,
-             /*a_off=*/p.implicit ? 0 : (int64_t)grp * Kgl,
+             /*lda=*/gather ? Kgl : p.ld_col, /*ldb=*/Kgl, /*ldc=*/Co,
+             /*a_off=*/gather ? 0 : (int64_t)grp * Kgl,
              /*b_off=*/(int64_t)grp * Cog * Kgl,
              /*c_off=*/(int64_t)grp * Cog,
-             true, true, 1.0f, 0.0f, p.implicit ? &ga : nullptr, nullptr,
+             true, true, 1.0f, 0.0f, gather ? &ga : nullptr, nullptr,
              fuse_relu);
   }
   if (!colT.defined())
@@ -474,19 +522,31 @@ Tensor conv2d_backward_weight_acc(const Tensor& x, const Tensor& colT,
                                   bool skip_unpack, bool skip_db) {
   check_float_like(dy, "dy");
   auto dy_cl = cl4(dy);
-  auto x_cl = cl4(x);
-  const ConvPlan p = conv_plan_for(x_cl.sizes(), (int)dw_out.size(0),
+  // "forward was implicit" / "forward was packed" come from the cache slot
+  // (empty 1-D sentinel / 4-D xp), not from the global switches: toggling
+  // one between forward and backward must stay harmless
+  const bool implicit = colT.numel() == 0 && colT.dim() == 1;
+  const bool packed = colT.dim() == 4;
+  const ConvPlan p = conv_plan_for(x.sizes(), (int)dw_out.size(0),
                                    (int)dw_out.size(2), (int)dw_out.size(3),
-                                   sh, sw, ph, pw, G, is_bf16(dy));
+                                   sh, sw, ph, pw, G, is_bf16(dy),
+                                   packed ? PS_PACKED_ON : PS_PACKED_OFF);
   TORCH_CHECK(dw_out.size(1) == p.Cg && dy_cl.size(2) == p.g.Ho &&
               dy_cl.size(3) == p.g.Wo, "conv wgrad: shape mismatch");
   const int Co = p.Co, Cog = p.Cog;
-  // "forward was implicit" comes from the cached colT sentinel, not from
-  // the plan: toggling the global flag between forward and backward must
-  // stay harmless
-  const bool implicit = colT.numel() == 0 && colT.dim() == 1;
-  TORCH_CHECK(implicit || colT.size(1) == p.ld_col,
-              "conv wgrad: colT width does not match the plan");
+  if (packed) {
+    TORCH_CHECK(p.packed && colT.is_contiguous() && is_bf16(colT) &&
+                colT.size(0) == p.g.N && colT.size(1) == p.g.H &&
+                colT.size(2) == p.pk_W && colT.size(3) == PS_PK_C,
+                "conv wgrad: packed input does not match the plan");
+  } else {
+    TORCH_CHECK(implicit || colT.size(1) == p.ld_col,
+                "conv wgrad: colT width does not match the plan");
+  }
+  // only the implicit gather reads x here: the materialized and the packed
+  // wgrad work from the cache slot alone (no layout copy of the data blob)
+  const Tensor xg = packed ? colT : implicit ? cl4(x) : Tensor();
+  const bool gather = implicit || packed;
   // colT may carry zero pad columns (ld_col): run the GEMM over the padded
   // width too (zero B columns -> zero dwk columns, skipped below).
   // Implicit wgrads pad the same way via the gather's kg_max bound, which
@@ -504,22 +564,22 @@ Tensor conv2d_backward_weight_acc(const Tensor& x, const Tensor& colT,
   for (int grp = 0; grp < G; ++grp) {
     // dwk_g[Cog, Kg] = dy_g^T[Cog, NP] @ colT_g[NP, Kg]: contraction NP
     GatherDesc gb{};
-    if (implicit)
-      gb = ps_gather_desc(p, PS_GATHER_WGRAD, x_cl.data_ptr(),
-                          zero_page(x_cl), grp);
-    run_gemm(dy2, implicit ? x_cl : colT, dwk, nullptr,
+    if (gather)
+      gb = ps_gather_desc(p, PS_GATHER_WGRAD, xg.data_ptr(), zero_page(xg),
+                          grp);
+    run_gemm(dy2, gather ? xg : colT, dwk, nullptr,
              Cog, Kgw, (int)p.NP,
-             /*lda=*/Co, /*ldb=*/implicit ? Kgw : p.ld_col, /*ldc=*/Kgw,
+             /*lda=*/Co, /*ldb=*/gather ? Kgw : p.ld_col, /*ldc=*/Kgw,
              /*a_off=*/(int64_t)grp * Cog,
-             /*b_off=*/implicit ? 0 : (int64_t)grp * Kgw,
+             /*b_off=*/gather ? 0 : (int64_t)grp * Kgw,
              /*c_off=*/(int64_t)grp * Cog * Kgw,
-             false, false, 1.0f, 0.0f, nullptr, implicit ? &gb : nullptr,
+             false, false, 1.0f, 0.0f, nullptr, gather ? &gb : nullptr,
              false, prez);
   }
   if (!skip_unpack)
     ps_weight_from_khwc_f32(dwk.data_ptr<float>(), dw_out.data_ptr<float>(),
                             Co, p.Cg, p.g.kh, p.g.kw, /*ld=*/Kgw,
-                            /*beta=*/1.0f, stream());
+                            /*beta=*/1.0f, p.kw_ld, p.c_ld, stream());
   if (db_out.has_value() && !skip_db)
     PS_CALL(colsum, is_bf16(dy_cl), P(dy_cl), db_out->data_ptr<float>(), p.NP,
             Co, stream());
@@ -1153,8 +1213,14 @@ std::vector<Tensor> unpack_mt_prepare(std::vector<Tensor> dwks,
                                       std::vector<Tensor> dws,
                                       std::vector<int64_t> Cigs,
                                       std::vector<int64_t> khs,
-                                      std::vector<int64_t> kws) {
+                                      std::vector<int64_t> kws,
+                                      std::vector<int64_t> kw_lds,
+                                      std::vector<int64_t> c_lds) {
   const size_t nt = dwks.size();
+  // khwc_layout() per tensor; empty = every conv plain (kw, Cig)
+  TORCH_CHECK((kw_lds.empty() && c_lds.empty()) ||
+              (kw_lds.size() == nt && c_lds.size() == nt),
+              "unpack_mt_prepare: layout length mismatch");
   std::vector<ps::MTUnpackDesc> descs(nt);
   for (size_t t = 0; t < nt; ++t) {
     TORCH_CHECK(dwks[t].is_cuda() && dwks[t].scalar_type() == at::kFloat &&
@@ -1165,8 +1231,13 @@ std::vector<Tensor> unpack_mt_prepare(std::vector<Tensor> dwks,
     int ldk = (int)dwks[t].size(1);
     int64_t n = dws[t].numel();
     TORCH_CHECK(n == (int64_t)Co * Cigs[t] * khs[t] * kws[t]);
+    const int kw_ld = kw_lds.empty() ? (int)kws[t] : (int)kw_lds[t];
+    const int c_ld = c_lds.empty() ? (int)Cigs[t] : (int)c_lds[t];
+    TORCH_CHECK(kw_ld >= kws[t] && c_ld >= Cigs[t] &&
+                (int64_t)khs[t] * kw_ld * c_ld <= ldk,
+                "unpack_mt_prepare: khwc layout exceeds the dwk row");
     descs[t] = {dwks[t].data_ptr<float>(), dws[t].data_ptr<float>(), n,
-                Co, (int)Cigs[t], (int)khs[t], (int)kws[t], ldk};
+                Co, (int)Cigs[t], (int)khs[t], (int)kws[t], ldk, kw_ld, c_ld};
   }
   return mt_tables(descs, dwks[0], mt_by_elts);
 }
@@ -1180,8 +1251,14 @@ void unpack_mt_run(const Tensor& desc_dev, const Tensor& chunk_dev,
 std::vector<Tensor> repack_mt_prepare(std::vector<Tensor> masters,
                                       std::vector<Tensor> wks,
                                       std::vector<Tensor> wkTs,
-                                      std::vector<int64_t> Gs) {
+                                      std::vector<int64_t> Gs,
+                                      std::vector<int64_t> kw_lds,
+                                      std::vector<int64_t> c_lds) {
   const size_t nt = masters.size();
+  // the plan's (kw_ld, c_ld) per tensor; empty = every shadow plain khwc
+  TORCH_CHECK((kw_lds.empty() && c_lds.empty()) ||
+              (kw_lds.size() == nt && c_lds.size() == nt),
+              "repack_mt_prepare: layout length mismatch");
   std::vector<ps::MTRepackDesc> descs(nt);
   for (size_t t = 0; t < nt; ++t) {
     const Tensor& m = masters[t];
@@ -1191,10 +1268,15 @@ std::vector<Tensor> repack_mt_prepare(std::vector<Tensor> masters,
                 "repack_mt_prepare: f32 NCHW masters + bf16 outputs");
     const bool has_t = wkTs[t].numel() > 0;
     TORCH_CHECK(!has_t || wkTs[t].scalar_type() == at::kBFloat16);
+    const int kw_ld = kw_lds.empty() ? (int)m.size(3) : (int)kw_lds[t];
+    const int c_ld = c_lds.empty() ? (int)m.size(1) : (int)c_lds[t];
+    TORCH_CHECK(kw_ld >= m.size(3) && c_ld >= m.size(1) &&
+                m.size(2) * kw_ld * c_ld <= wks[t].size(1),
+                "repack_mt_prepare: khwc layout exceeds the wk row");
     descs[t] = {m.data_ptr<float>(), wks[t].data_ptr(),
                 has_t ? wkTs[t].data_ptr() : nullptr,
                 m.numel(), (int)m.size(0), (int)m.size(1), (int)m.size(2),
-                (int)m.size(3), (int)Gs[t], (int)wks[t].size(1)};
+                (int)m.size(3), (int)Gs[t], (int)wks[t].size(1), kw_ld, c_ld};
   }
   return mt_tables(descs, masters[0], mt_by_elts);
 }
@@ -1226,6 +1308,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("conv2d_backward_weight_acc", &conv2d_backward_weight_acc);
   m.def("set_implicit_gemm", &set_implicit_gemm);
   m.def("set_implicit_threshold", &set_implicit_threshold);
+  m.def("set_packed_conv", &set_packed_conv);
+  m.def("khwc_layout", &khwc_layout);
+  // one process can run either conv1 path: env overrides, read once here
+  if (const char* e = std::getenv("PS_PACKED_CONV"))
+    set_packed_conv(std::atoi(e) != 0);
   m.def("set_dgrad_fwd_threshold", &set_dgrad_fwd_threshold);
   m.def("concat_channels", &concat_channels);
   m.def("slice_channels", &slice_channels);

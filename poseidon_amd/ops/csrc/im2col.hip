@@ -106,8 +106,45 @@ __device__ inline int fdiv_fix2(int x2, int d, float inv, int& rem) {
   return q;
 }
 
-// LDS row-staged variant for small-C first layers (G==1, C % 8 != 0 --
-// conv1-style). The rowrun kernel above issues unaligned 16 B ops on 66 B
+// Packed first-layer input (ps_conv_plan.h, PS_PK_SLOTS): x -> xp[N][H][Wp][8],
+// two adjacent pixels of 4 channel slots per 16 B chunk, the left padding
+// baked in. One thread per chunk: reads follow x's own strides (NCHW reads
+// are contiguous along w per channel plane, NHWC ones contiguous outright),
+// every store is one aligned 16 B chunk. Pad pixels, unused slots and the
+// pixels past the right edge are zeros. Replaces the channels-last copy AND
+// the im2col of the layers that take the packed plan.
+__global__ void pack_pairs_k(const __bf16* __restrict__ x,
+                             __bf16* __restrict__ xp, int N, int C, int H,
+                             int W, int Wp, int pw, int64_t sn, int64_t sc,
+                             int64_t sh, int64_t sw) {
+  const int64_t total = (int64_t)N * H * Wp;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total;
+       i += (int64_t)gridDim.x * blockDim.x) {
+    const int wp = (int)(i % Wp);
+    const int64_t t = i / Wp;
+    const int h = (int)(t % H);
+    const int64_t n = t / H;
+    const __bf16* row = x + n * sn + h * sh;
+    bf16x8 v;
+#pragma unroll
+    for (int half = 0; half < 2; ++half) {
+      const int iw = 2 * wp + half - pw;  // inverse of ps_pk_chunk/ps_pk_half
+      const bool in = iw >= 0 && iw < W;
+#pragma unroll
+      for (int c = 0; c < PS_PK_SLOTS; ++c)
+        v[half * PS_PK_SLOTS + c] =
+            (in && c < C) ? row[c * sc + iw * sw] : (__bf16)0.0f;
+    }
+    *reinterpret_cast<bf16x8*>(&xp[i * PS_PK_C]) = v;
+  }
+}
+
+// LDS row-staged variant for small-C first layers (G==1, C % 8 != 0).
+// With the packed switch at its default (off) that is every first layer:
+// AlexNet/CaffeNet/GoogLeNet conv1, VGG conv1_1, CIFAR, LeNet. With it on,
+// the even-stride bf16 ones (AlexNet/CaffeNet/GoogLeNet conv1) leave for
+// the packed plan; stride-1 and fp32 layers stay here.
+// The rowrun kernel above issues unaligned 16 B ops on 66 B
 // runs (every op splits into two requests) and re-reads overlapping
 // windows from HBM; here a block stages the kh input rows of one (n, oh)
 // in LDS once (coalesced), then emits the (Wo x Kcol) output span as
@@ -116,7 +153,11 @@ __device__ inline int fdiv_fix2(int x2, int d, float inv, int& rem) {
 template <typename T>
 __global__ void im2col_rowstage_k(const T* __restrict__ x,
                                   T* __restrict__ colT, ConvGeom g,
-                                  int rsw, int ldcol) {
+                                  int rsw, int ldcol, int64_t sn, int64_t sc,
+                                  int64_t sh, int64_t sw) {
+  // x is read through its element strides (sn, sc, sh, sw): the data blob
+  // arrives NCHW, and staging it from there saves the channels-last copy
+  // the first layer would otherwise make of it every step
   extern __shared__ char smem[];
   T* xs = (T*)smem;  // [kh][rsw]; staged elem s <-> iw_elem = s - pw*C
   constexpr int V = 16 / (int)sizeof(T);
@@ -137,14 +178,18 @@ __global__ void im2col_rowstage_k(const T* __restrict__ x,
       if (ih < 0 || ih >= g.H) {
         for (int e = threadIdx.x; e < rsw; e += blockDim.x) row[e] = (T)0.0f;
       } else {
-        const T* src = x + (((int64_t)n * g.H + ih) * g.W) * g.C - g.pw * g.C;
+        const T* src = x + n * sn + ih * sh;
+        const float inv_C = 1.0f / g.C;
         for (int e = threadIdx.x * V; e < rsw; e += blockDim.x * V) {
           uvec_t v;
+          int c;
+          int iw = fdiv_fix2(e, g.C, inv_C, c) - g.pw;  // staged elem e
 #pragma unroll
           for (int j2 = 0; j2 < V; ++j2) {
             const int ie = e + j2 - g.pw * g.C;
-            v[j2] = (ie >= 0 && ie < WC && e + j2 < rsw) ? src[e + j2 + 0]
-                                                         : (T)0.0f;
+            v[j2] = (ie >= 0 && ie < WC && e + j2 < rsw)
+                        ? src[iw * sw + c * sc] : (T)0.0f;
+            if (++c == g.C) { c = 0; ++iw; }
           }
           if (e + V <= rsw)
             *reinterpret_cast<uvec_t*>(&row[e]) = v;
@@ -320,11 +365,13 @@ __global__ void weight_to_khwc_tr_k(const TI* src, TO* dst, int Co, int Cig,
 // Fused repack: one read of the fp32 master emits BOTH the khwc forward
 // operand and its per-group transpose for dgrad (they were two kernels =
 // two master reads + two launches per conv per iteration; GoogLeNet has 59
-// convs).
+// convs). The khwc rows take the plan's tap-row width and channel slots
+// (kw_ld, c_ld: wider than (KW, Cig) for a packed first layer, whose other
+// columns the caller zeroed); the dgrad transpose is always plain.
 template <typename TI, typename TO>
 __global__ void weight_to_khwc_both_k(const TI* src, TO* dst, TO* dst_tr,
                                       int Co, int Cig, int KH, int KW, int G,
-                                      int ldk) {
+                                      int ldk, int kw_ld, int c_ld) {
   const int Cog = Co / G;
   const int Kg = KH * KW * Cig;
   int64_t total = (int64_t)Co * Kg;
@@ -337,7 +384,8 @@ __global__ void weight_to_khwc_both_k(const TI* src, TO* dst, TO* dst_tr,
     int co = t / Cig;
     const float v = to_f32(src[i]);
     const int kg = (kkh * KW + kkw) * Cig + ci;
-    from_f32(v, dst[(int64_t)co * ldk + kg]);
+    from_f32(v, dst[(int64_t)co * ldk +
+                    ps_khwc_col(kkh, kkw, ci, kw_ld, c_ld)]);
     from_f32(v, dst_tr[((int64_t)(co / Cog) * Kg + kg) * Cog + co % Cog]);
   }
 }
@@ -378,7 +426,8 @@ __global__ void weight_to_dgrad_k(const TI* src, TO* dst, int Co, int Cig,
 
 template <typename TI, typename TO>
 __global__ void weight_from_khwc_k(const TI* src, TO* dst, int Co, int Cig,
-                                   int KH, int KW, int ld, float beta) {
+                                   int KH, int KW, int ld, float beta,
+                                   int kw_ld, int c_ld) {
   int64_t total = (int64_t)Co * Cig * KH * KW;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total;
        i += (int64_t)gridDim.x * blockDim.x) {
@@ -387,7 +436,7 @@ __global__ void weight_from_khwc_k(const TI* src, TO* dst, int Co, int Cig,
     int kkh = t % KH; t /= KH;
     int ci = t % Cig;
     int co = t / Cig;
-    int64_t src_i = (int64_t)co * ld + ((int64_t)kkh * KW + kkw) * Cig + ci;
+    int64_t src_i = (int64_t)co * ld + ps_khwc_col(kkh, kkw, ci, kw_ld, c_ld);
     float v = to_f32(src[src_i]);
     if (beta != 0.f) v += beta * to_f32(dst[i]);
     from_f32(v, dst[i]);
@@ -493,7 +542,38 @@ __global__ void chan_slice_k(const T* __restrict__ in, T* __restrict__ out,
   }
 }
 
+// The rowstage im2col reading x through element strides (sn, sc, sh, sw) --
+// NHWC or the NCHW the data blob arrives in. Its shapes: G == 1, channel
+// runs that are no 16 B multiple, kh staged rows within 48 KB of LDS.
+// Returns false, launching nothing, for any other shape.
+template <typename T>
+static bool im2col_rowstage(const T* x, T* colT, const ConvGeom* g, int ldcol,
+                            int64_t sn, int64_t sc, int64_t sh, int64_t sw,
+                            hipStream_t s) {
+  if (g->G != 1 || g->C % (16 / (int)sizeof(T)) == 0) return false;
+  int rsw = ((g->Wo - 1) * g->sw + g->kw) * g->C;
+  int64_t lds = (int64_t)g->kh * rsw * sizeof(T);
+  if (lds > (48 << 10)) return false;
+  int64_t blocks = (int64_t)g->N * g->Ho;
+  if (blocks > (64 << 10)) blocks = 64 << 10;
+  im2col_rowstage_k<T><<<dim3((unsigned)blocks), 256, lds, s>>>(
+      x, colT, *g, rsw, ldcol, sn, sc, sh, sw);
+  return true;
+}
+
 extern "C" {
+
+bool ps_im2col_rowstage_f32(const float* x, float* colT, const ConvGeom* g,
+                            int ldcol, int64_t sn, int64_t sc, int64_t sh,
+                            int64_t sw, hipStream_t s) {
+  return im2col_rowstage<float>(x, colT, g, ldcol, sn, sc, sh, sw, s);
+}
+bool ps_im2col_rowstage_bf16(const void* x, void* colT, const ConvGeom* g,
+                             int ldcol, int64_t sn, int64_t sc, int64_t sh,
+                             int64_t sw, hipStream_t s) {
+  return im2col_rowstage<__bf16>((const __bf16*)x, (__bf16*)colT, g, ldcol,
+                                 sn, sc, sh, sw, s);
+}
 
 // n <= 4 narrow tensors <-> one wide tensor in a single launch.
 // Requirements checked by caller: every range width and boundary divisible
@@ -588,18 +668,11 @@ void ps_im2col_nhwc_f32(const float* x, float* colT, const ConvGeom* g,
   if (Cg % 4 == 0)
     im2col_nhwc_k<float, 4><<<ew_grid(base * (Cg / 4)), 256, 0, s>>>(x, colT, *g, ldcol);
   else if (g->G == 1) {
-    int rsw = ((g->Wo - 1) * g->sw + g->kw) * g->C;
-    int64_t lds = (int64_t)g->kh * rsw * sizeof(float);
-    if (lds <= (48 << 10)) {
-      int64_t blocks = (int64_t)g->N * g->Ho;
-      if (blocks > (64 << 10)) blocks = 64 << 10;
-      im2col_rowstage_k<float>
-          <<<dim3((unsigned)blocks), 256, lds, s>>>(x, colT, *g, rsw, ldcol);
-    } else {
+    if (!ps_im2col_rowstage_f32(x, colT, g, ldcol, (int64_t)g->H * g->W * g->C,
+                                1, (int64_t)g->W * g->C, g->C, s))
       im2col_nhwc_rowrun_k<float, 16>
           <<<ew_grid((int64_t)g->N * g->Ho * g->Wo * g->kh), 256, 0, s>>>(
               x, colT, *g, ldcol);
-    }
   }
   else
     im2col_nhwc_k<float, 1><<<ew_grid(base * Cg), 256, 0, s>>>(x, colT, *g, ldcol);
@@ -612,20 +685,12 @@ void ps_im2col_nhwc_bf16(const void* x, void* colT, const ConvGeom* g,
     im2col_nhwc_k<__bf16, 8><<<ew_grid(base * (Cg / 8)), 256, 0, s>>>(
         (const __bf16*)x, (__bf16*)colT, *g, ldcol);
   else if (g->G == 1) {
-    int rsw = ((g->Wo - 1) * g->sw + g->kw) * g->C;
-    int64_t lds = (int64_t)g->kh * rsw * sizeof(__bf16);
-    if (lds <= (48 << 10)) {
-      int64_t blocks = (int64_t)g->N * g->Ho;
-      if (blocks > (64 << 10)) blocks = 64 << 10;
-      im2col_rowstage_k<__bf16>
-          <<<dim3((unsigned)blocks), 256, lds, s>>>((const __bf16*)x,
-                                                    (__bf16*)colT, *g, rsw,
-                                                    ldcol);
-    } else {
+    if (!ps_im2col_rowstage_bf16(x, colT, g, ldcol,
+                                 (int64_t)g->H * g->W * g->C, 1,
+                                 (int64_t)g->W * g->C, g->C, s))
       im2col_nhwc_rowrun_k<__bf16, 16>
           <<<ew_grid((int64_t)g->N * g->Ho * g->Wo * g->kh), 256, 0, s>>>(
               (const __bf16*)x, (__bf16*)colT, *g, ldcol);
-    }
   }
   else
     im2col_nhwc_k<__bf16, 1><<<ew_grid(base * Cg), 256, 0, s>>>(
@@ -674,17 +739,25 @@ void ps_weight_to_khwc_tr_f32_bf16(const float* src, void* dst, int Co, int Cig,
 }
 void ps_weight_to_khwc_both_f32(const float* src, float* dst, float* dst_tr,
                                 int Co, int Cig, int KH, int KW, int G,
-                                int ldk, hipStream_t s) {
+                                int ldk, int kw_ld, int c_ld, hipStream_t s) {
   weight_to_khwc_both_k<float, float>
       <<<ew_grid((int64_t)Co * Cig * KH * KW), 256, 0, s>>>(
-          src, dst, dst_tr, Co, Cig, KH, KW, G, ldk);
+          src, dst, dst_tr, Co, Cig, KH, KW, G, ldk, kw_ld, c_ld);
 }
 void ps_weight_to_khwc_both_f32_bf16(const float* src, void* dst,
                                      void* dst_tr, int Co, int Cig, int KH,
-                                     int KW, int G, int ldk, hipStream_t s) {
+                                     int KW, int G, int ldk, int kw_ld,
+                                     int c_ld, hipStream_t s) {
   weight_to_khwc_both_k<float, __bf16>
       <<<ew_grid((int64_t)Co * Cig * KH * KW), 256, 0, s>>>(
-          src, (__bf16*)dst, (__bf16*)dst_tr, Co, Cig, KH, KW, G, ldk);
+          src, (__bf16*)dst, (__bf16*)dst_tr, Co, Cig, KH, KW, G, ldk, kw_ld,
+          c_ld);
+}
+void ps_pack_pairs_bf16(const void* x, void* xp, int N, int C, int H, int W,
+                        int Wp, int pw, int64_t sn, int64_t sc, int64_t sh,
+                        int64_t sw, hipStream_t s) {
+  pack_pairs_k<<<ew_grid((int64_t)N * H * Wp), 256, 0, s>>>(
+      (const __bf16*)x, (__bf16*)xp, N, C, H, W, Wp, pw, sn, sc, sh, sw);
 }
 void ps_zero_cols_f32(float* m, int64_t rows, int ld, int c_lo,
                       hipStream_t s) {
@@ -711,11 +784,11 @@ void ps_weight_to_dgrad_f32_bf16(const float* src, void* dst, int Co,
           src, (__bf16*)dst, Co, Cig, KH, KW, G);
 }
 void ps_weight_from_khwc_f32(const float* src, float* dst, int Co, int Cig,
-                             int KH, int KW, int ld, float beta,
-                             hipStream_t s) {
+                             int KH, int KW, int ld, float beta, int kw_ld,
+                             int c_ld, hipStream_t s) {
   weight_from_khwc_k<float, float>
-      <<<ew_grid((int64_t)Co * Cig * KH * KW), 256, 0, s>>>(src, dst, Co, Cig,
-                                                            KH, KW, ld, beta);
+      <<<ew_grid((int64_t)Co * Cig * KH * KW), 256, 0, s>>>(
+          src, dst, Co, Cig, KH, KW, ld, beta, kw_ld, c_ld);
 }
 
 }  // extern "C"

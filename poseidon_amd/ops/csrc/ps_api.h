@@ -179,6 +179,13 @@ void ps_chan_slice_f32(const float*, float*, int64_t, int, int, int, hipStream_t
 void ps_chan_slice_bf16(const void*, void*, int64_t, int, int, int, hipStream_t);
 void ps_im2col_nhwc_f32(const float*, float*, const ConvGeom*, int ldcol,
                         hipStream_t);
+// rowstage im2col through x's element strides; false = not its shape
+bool ps_im2col_rowstage_f32(const float*, float*, const ConvGeom*, int ldcol,
+                            int64_t sn, int64_t sc, int64_t sh, int64_t sw,
+                            hipStream_t);
+bool ps_im2col_rowstage_bf16(const void*, void*, const ConvGeom*, int ldcol,
+                             int64_t sn, int64_t sc, int64_t sh, int64_t sw,
+                             hipStream_t);
 void ps_col2im_nhwc_f32(const float*, float*, const ConvGeom*, hipStream_t);
 void ps_im2col_nhwc_bf16(const void*, void*, const ConvGeom*, int ldcol,
                          hipStream_t);
@@ -192,13 +199,20 @@ void ps_weight_to_dgrad_f32(const float*, float*, int, int, int, int, int,
 void ps_weight_to_dgrad_f32_bf16(const float*, void*, int, int, int, int,
                                  int, hipStream_t);
 void ps_weight_from_khwc_f32(const float*, float*, int, int, int, int,
-                             int ld, float beta, hipStream_t);
+                             int ld, float beta, int kw_ld, int c_ld,
+                             hipStream_t);
 void ps_weight_to_khwc_tr_f32(const float*, float*, int, int, int, int, int,
                               hipStream_t);
 void ps_weight_to_khwc_tr_f32_bf16(const float*, void*, int, int, int, int,
                                    int, hipStream_t);
 void ps_weight_to_khwc_both_f32(const float*, float*, float*, int, int, int,
-                                int, int, int ldk, hipStream_t);
+                                int, int, int ldk, int kw_ld, int c_ld,
+                                hipStream_t);
 void ps_weight_to_khwc_both_f32_bf16(const float*, void*, void*, int, int,
-                                     int, int, int, int ldk, hipStream_t);
+                                     int, int, int, int ldk, int kw_ld,
+                                     int c_ld, hipStream_t);
+// x (bf16, element strides sn/sc/sh/sw) -> xp[N][H][Wp][8]
+void ps_pack_pairs_bf16(const void* x, void* xp, int N, int C, int H, int W,
+                        int Wp, int pw, int64_t sn, int64_t sc, int64_t sh,
+                        int64_t sw, hipStream_t);
 }

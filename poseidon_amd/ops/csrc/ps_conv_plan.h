@@ -5,6 +5,12 @@
 #pragma once
 #include <cstdint>
 
+#if defined(__HIPCC__)
+#define PS_HD __host__ __device__
+#else
+#define PS_HD
+#endif
+
 struct ConvGeom {
   int N, C, H, W;
   int Ho, Wo;
@@ -39,7 +45,41 @@ struct ConvPolicy {
   bool force_implicit;      // global implicit-GEMM switch
   int64_t implicit_bytes;   // colT above this goes implicit per layer
   int64_t dgrad_fwd_bytes;  // dcolT above this runs dgrad as a forward conv
+  bool packed;              // packed small-channel first-layer switch
 };
+
+// Packed first-layer layout (G==1, C <= 4, even sw): x is copied once into
+// xp[N][H][Wp][8], each 16 B chunk holding two horizontally adjacent pixels
+// of PS_PK_SLOTS channel slots, the left padding pw baked in as zero pixels.
+// The kh x kw / stride (sh, sw) conv over x is then EXACTLY a
+// kh x ceil(kw/2) / stride (sh, sw/2) / pad (ph, 0) conv with 8 channels
+// over xp, which the gather GEMMs run with 16 B-aligned chunks and no
+// column matrix. Unused slots and the phantom tap kx == kw of an odd kw
+// carry zero weights.
+constexpr int PS_PK_SLOTS = 4;               // channel slots per pixel
+constexpr int PS_PK_C = 2 * PS_PK_SLOTS;     // channels of xp (one chunk)
+
+// pixel iw of x -> chunk and half-chunk of an xp row
+PS_HD inline int ps_pk_chunk(int iw, int pw) { return (iw + pw) >> 1; }
+PS_HD inline int ps_pk_half(int iw, int pw) { return (iw + pw) & 1; }
+// element index of x[n][c][ih][iw] in xp
+PS_HD inline int64_t ps_pk_x_index(int n, int ih, int iw, int c, int H,
+                                   int Wp, int pw) {
+  return (((int64_t)n * H + ih) * Wp + ps_pk_chunk(iw, pw)) * PS_PK_C +
+         ps_pk_half(iw, pw) * PS_PK_SLOTS + c;
+}
+// khwc weight rows: column of tap (ky, kx, c) for a tap-row width kw_ld and
+// c_ld channel slots. Plain khwc is (kw, Cg); the packed layout is
+// (2 * pk_kw, PS_PK_SLOTS), which makes it the (ky, kx/2, 8-channel) order
+// the gather decodes.
+PS_HD inline int ps_khwc_col(int ky, int kx, int c, int kw_ld, int c_ld) {
+  return (ky * kw_ld + kx) * c_ld + c;
+}
+inline void ps_khwc_layout(int kw, int Cg, bool packed, int* kw_ld,
+                           int* c_ld) {
+  *kw_ld = packed ? 2 * ((kw + 1) / 2) : kw;
+  *c_ld = packed ? PS_PK_SLOTS : Cg;
+}
 
 struct ConvPlan {
   ConvGeom g;
@@ -62,6 +102,13 @@ struct ConvPlan {
   // stride-1 dgrad as a FORWARD conv of dy with rotated weights
   // (dx = conv(dy, rot180 W, pad = k-1-p)) through the gather GEMM
   bool dgrad_as_fwd;
+  // packed first layer (see PS_PK_SLOTS): forward and wgrad gather from xp.
+  // wk_ld then is the packed row width, pk_Kg rounded up to 64
+  bool packed;
+  int pk_W;         // Wp: 16 B chunks per xp row
+  int pk_kw;        // kw': taps per row in chunks, ceil(kw / 2)
+  int pk_Kg;        // kh * pk_kw * 8
+  int kw_ld, c_ld;  // khwc tap-row width and channel slots (ps_khwc_col)
 };
 
 inline ConvPlan ps_conv_plan(int N, int C, int H, int W, int Co, int kh,
@@ -85,6 +132,20 @@ inline ConvPlan ps_conv_plan(int N, int C, int H, int W, int Co, int kh,
   p.implicit = (policy.force_implicit || colT_bytes > policy.implicit_bytes) &&
                !p.is_1x1 && p.Cg % p.vec == 0;
   p.Kgw_implicit = (p.Kg + 63) & ~63;
+  // packing needs whole pixel pairs per stride step (even sw). The dgrad
+  // of such a conv, if anyone asks for it, takes the unpacked path.
+  p.packed = policy.packed && G == 1 &&
+             C <= PS_PK_SLOTS && elem_bytes == 2 && sw % 2 == 0 && !p.is_1x1 &&
+             p.g.Ho > 0 && p.g.Wo > 0;
+  p.pk_kw = (kw + 1) / 2;
+  p.pk_W = (p.g.Wo - 1) * (sw / 2) + p.pk_kw;
+  p.pk_Kg = kh * p.pk_kw * PS_PK_C;
+  ps_khwc_layout(kw, p.Cg, p.packed, &p.kw_ld, &p.c_ld);
+  if (p.packed) {
+    p.implicit = false;
+    p.wk_ld = (p.pk_Kg + 63) & ~63;
+    p.kpad = true;  // unused slots / phantom taps / pad columns stay zero
+  }
   // worth it only when the dcolT it eliminates is substantial (small
   // inception dgrads measured faster on the materialized NT + col2im)
   p.dgrad_as_fwd = sh == 1 && sw == 1 && !p.is_1x1 && p.Cog % p.vec == 0 &&
@@ -94,7 +155,7 @@ inline ConvPlan ps_conv_plan(int N, int C, int H, int W, int Co, int kh,
 }
 
 enum ConvGatherRole {
-  PS_GATHER_FWD,           // A rows gathered from x
+  PS_GATHER_FWD,           // A rows gathered from x (xp for a packed plan)
   PS_GATHER_WGRAD,         // K-major B gathered from x (same window as fwd)
   PS_GATHER_DGRAD_AS_FWD,  // A rows gathered from dy, roles of x/y swapped
 };
@@ -112,6 +173,13 @@ inline GatherDesc ps_gather_desc(const ConvPlan& p, ConvGatherRole role,
     d.sh = 1; d.sw = 1; d.ph = g.kh - 1 - g.ph; d.pw = g.kw - 1 - g.pw;
     d.Cg = p.Cog; d.c0 = grp * p.Cog;
     d.kg_max = g.kh * g.kw * p.Cog;
+  } else if (p.packed) {
+    // x is xp: the equivalent 8-channel conv over chunk columns
+    d.kw = p.pk_kw;
+    d.C = PS_PK_C; d.H = g.H; d.W = p.pk_W; d.Ho = g.Ho; d.Wo = g.Wo;
+    d.sh = g.sh; d.sw = g.sw / 2; d.ph = g.ph; d.pw = 0;
+    d.Cg = PS_PK_C; d.c0 = 0;
+    d.kg_max = p.pk_Kg;
   } else {
     d.C = g.C; d.H = g.H; d.W = g.W; d.Ho = g.Ho; d.Wo = g.Wo;
     d.sh = g.sh; d.sw = g.sw; d.ph = g.ph; d.pw = g.pw;

@@ -5,6 +5,8 @@
 #pragma once
 #include <cstdint>
 
+#include "ps_conv_plan.h"  // ps_khwc_col
+
 namespace ps {
 
 // elements per workgroup: 256 threads x vec4 x 8 iters
@@ -38,6 +40,7 @@ struct MTRepackDesc {
   void* wkT;         // bf16 [G*Kg][Cog]
   int64_t n;         // Co*Cig*kh*kw
   int Co, Cig, kh, kw, G, ldk;
+  int kw_ld, c_ld;   // wk tap-row width / channel slots (ps_khwc_col)
 };
 
 // inverse of the repack for GRADIENTS: khwc fp32 wgrad scratch -> NCHW
@@ -46,6 +49,7 @@ struct MTUnpackDesc {
   float* dw;         // fp32 NCHW [Co][Cig][kh][kw], accumulated into
   int64_t n;         // Co*Cig*kh*kw
   int Co, Cig, kh, kw, ldk;
+  int kw_ld, c_ld;   // dwk tap-row width / channel slots (ps_khwc_col)
 };
 
 // bias colsum; its chunks count ROWS (ColsumChunk.off = start row)

@@ -148,7 +148,8 @@ __global__ void repack_mt_k(const MTRepackDesc* __restrict__ descs,
     int co = (int)(t / Cig);
     const float v = d.src[i];
     const int kg = (kkh * KW + kkw) * Cig + ci;
-    ((__bf16*)d.wk)[(int64_t)co * d.ldk + kg] = (__bf16)v;
+    ((__bf16*)d.wk)[(int64_t)co * d.ldk +
+                    ps_khwc_col(kkh, kkw, ci, d.kw_ld, d.c_ld)] = (__bf16)v;
     if (d.wkT)  // IP shadows need only the row-major form
       ((__bf16*)d.wkT)[((int64_t)(co / Cog) * Kg + kg) * Cog + co % Cog] =
           (__bf16)v;
@@ -171,8 +172,8 @@ __global__ void unpack_mt_k(const MTUnpackDesc* __restrict__ descs,
     int kkh = (int)(t % KH); t /= KH;
     int ci = (int)(t % Cig);
     int co = (int)(t / Cig);
-    const int kg = (kkh * KW + kkw) * Cig + ci;
-    d.dw[i] += d.dwk[(int64_t)co * d.ldk + kg];
+    d.dw[i] += d.dwk[(int64_t)co * d.ldk +
+                     ps_khwc_col(kkh, kkw, ci, d.kw_ld, d.c_ld)];
   }
 }
 

@@ -55,6 +55,32 @@ def set_implicit_threshold(bytes_: int) -> None:
         _ext().set_implicit_threshold(int(bytes_))
 
 
+# bumped by every setter that can change a conv's khwc weight layout: Net
+# keys its persistent wk buffers on it
+_conv_policy_epoch = 0
+
+
+def set_packed_conv(on: bool) -> None:
+    """Toggle the packed first-layer path (G==1, C<=4, even horizontal
+    stride, bf16): forward and wgrad gather from a pair-packed copy of the
+    input instead of building a column matrix. Default off (it measures
+    slower on AlexNet conv1, docs/performance.md item 20); the environment
+    variable PS_PACKED_CONV=0/1 sets it at import."""
+    global _conv_policy_epoch
+    _ext().set_packed_conv(bool(on))
+    _conv_policy_epoch += 1
+
+
+def conv_policy_epoch() -> int:
+    return _conv_policy_epoch
+
+
+def khwc_layout(Cg: int, kw: int, packed: bool) -> Tuple[int, int]:
+    """(tap-row width, channel slots) of a conv's khwc weight rows."""
+    kw_ld, c_ld = _ext().khwc_layout(int(Cg), int(kw), bool(packed))
+    return int(kw_ld), int(c_ld)
+
+
 DGRAD_FWD_THRESHOLD_DEFAULT = 128 << 20
 
 
@@ -98,8 +124,11 @@ def conv2d_forward_ex(x: torch.Tensor, w: torch.Tensor, b: Optional[torch.Tensor
                       stride: Tuple[int, int], pad: Tuple[int, int],
                       groups: int, fuse_relu: bool = False, cached=None):
     """Returns (y, colT_cache). colT is the im2col matrix on GPU (reused by
-    the backward GEMMs); None on CPU. fuse_relu clamps the output in the
-    GEMM epilogue (used by the Net-level conv+ReLU fusion pass)."""
+    the backward GEMMs) -- or, in its place, the empty implicit-GEMM
+    sentinel or the 4-D packed input of a packed first layer, which tell
+    the wgrad what the forward did; None on CPU. fuse_relu clamps the
+    output in the GEMM epilogue (used by the Net-level conv+ReLU fusion
+    pass)."""
     if x.is_cuda:
         wk_c, wkT_c = cached if cached is not None else (None, None)
         y, colT, wkT = _ext().conv2d_forward_ex(x, w, b, stride[0], stride[1],
@@ -543,9 +572,13 @@ def conv_plan(x_shape, w_shape, stride, pad, groups: int, bf16: bool) -> dict:
                             list(pad), int(groups), bool(bf16))
 
 
-def repack_mt_prepare(masters, wks, wkTs, Gs):
+def repack_mt_prepare(masters, wks, wkTs, Gs, kw_lds=(), c_lds=()):
+    """kw_lds / c_lds: the plan's khwc layout per tensor (conv_plan's kw_ld,
+    c_ld); empty means every shadow is plain khwc."""
     d, c, n = _ext().repack_mt_prepare(list(masters), list(wks), list(wkTs),
-                                       [int(g) for g in Gs])
+                                       [int(g) for g in Gs],
+                                       [int(v) for v in kw_lds],
+                                       [int(v) for v in c_lds])
     return d, c, int(n.item())
 
 
@@ -554,9 +587,12 @@ def repack_mt_run(mt) -> None:
     _ext().repack_mt_run(d, c, n)
 
 
-def unpack_mt_prepare(dwks, dws, Cigs, khs, kws):
+def unpack_mt_prepare(dwks, dws, Cigs, khs, kws, kw_lds=(), c_lds=()):
+    """kw_lds / c_lds: khwc_layout() of each dwk scratch; empty = plain."""
     d, c, n = _ext().unpack_mt_prepare(list(dwks), list(dws), list(Cigs),
-                                       list(khs), list(kws))
+                                       list(khs), list(kws),
+                                       [int(v) for v in kw_lds],
+                                       [int(v) for v in c_lds])
     return d, c, int(n)
 
 
