@@ -1307,6 +1307,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("conv2d_backward_input", &conv2d_backward_input);
   m.def("conv2d_backward_weight_acc", &conv2d_backward_weight_acc);
   m.def("set_implicit_gemm", &set_implicit_gemm);
+  // tests / tuning: force the tr16 TN tile and its split-K block target
+  // (all 0 = the planner's choice)
+  m.def("set_tr16_tune", &ps_gemm_set_tr_tune);
   m.def("set_implicit_threshold", &set_implicit_threshold);
   m.def("set_packed_conv", &set_packed_conv);
   m.def("khwc_layout", &khwc_layout);

@@ -23,6 +23,8 @@
 // conv_layer.cu:25-121, inner_product_layer.cu:18-63).
 
 #include <algorithm>
+#include <cstdio>
+#include <cstdlib>
 #include <type_traits>
 
 #include "ps_common.h"
@@ -768,6 +770,53 @@ __device__ inline void tr_wait(bf16x8 (&a)[NA], bf16x8 (&b)[NB]) {
   for (int i = 0; i < NB; ++i) asm volatile("" : "+v"(b[i]));
 }
 
+// A panel of W > 64 columns is staged as 64-column sub-images (96 = 64 +
+// 32), each a [64][COLS] image with its OWN tr_swz, laid one after the
+// other; a fragment (16 columns) never straddles two of them. Two reasons:
+// stage_kmaj_tr needs COLS / 8 to divide 64 (96, 192), and a 128-column
+// image has 256 B rows -- every row starts on bank 0 and tr_swz's two row
+// bits leave a 4-way conflict (measured 2-4 conflict cycles per MFMA on the
+// 32x128 / 64x128 tiles against 0.0 on 64x64), which 128 B rows do not have.
+// A sub-image that starts at or past cmax (ragged last N tile,
+// ps_tr_sub_live) is not staged at all: only dead waves would read it.
+template <int W, bool GATHER = false, bool NT = false>
+__device__ inline void stage_panel_tr(__bf16* lds, const __bf16* src,
+                                      int64_t ld, int k0, int c0, int cmax,
+                                      int wid, int lane,
+                                      const GatherDesc* ga = nullptr) {
+  if constexpr (W <= 64) {
+    stage_kmaj_tr<W, GATHER, NT>(lds, src, ld, k0, c0, wid, lane, ga);
+  } else {
+#pragma unroll
+    for (int i = 0; i < W / 64; ++i)
+      if (ps_tr_sub_live(c0, i, cmax))
+        stage_kmaj_tr<64, GATHER, NT>(lds + i * 64 * 64, src, ld, k0,
+                                      c0 + i * 64, wid, lane, ga);
+    if constexpr (W % 64 != 0)
+      stage_kmaj_tr<W % 64, GATHER, NT>(lds + (W / 64) * 64 * 64, src, ld,
+                                        k0, c0 + (W / 64) * 64, wid, lane,
+                                        ga);
+  }
+}
+
+template <int W>
+__device__ inline bf16x8 tr_panel_frag(unsigned lds_base, int kk, int cb,
+                                       int l) {
+  if constexpr (W <= 64) {
+    return tr_frag<W>(lds_base, kk, cb, l, W);
+  } else if constexpr (W % 64 == 0) {
+    return tr_frag<64>(lds_base + (unsigned)(cb >> 6) * (64 * 64 * 2), kk,
+                       cb & 63, l, 64);
+  } else {
+    constexpr int FULL = W / 64 * 64;  // columns in whole sub-images
+    if (cb < FULL)
+      return tr_frag<64>(lds_base + (unsigned)(cb >> 6) * (64 * 64 * 2), kk,
+                         cb & 63, l, 64);
+    return tr_frag<W % 64>(lds_base + FULL * 64 * 2, kk, cb - FULL, l,
+                           W % 64);
+  }
+}
+
 template <int BM2, int BN2, int WGM2, int WGN2, bool SPLITK,
           bool GB2 = false>
 __global__ __launch_bounds__(256)
@@ -814,11 +863,14 @@ void gemm_tn_tr_kernel(const __bf16* __restrict__ A,
   }
   const int tid = threadIdx.x;
   const int lane = tid & 63;
-  const int wid = tid >> 6;
-  const int wm = (wid / WGN2) * (BM2 / WGM2);
+  const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int wm = WGM2 == 1 ? 0 : (wid / WGN2) * (BM2 / WGM2);
   const int wn = (wid % WGN2) * (BN2 / WGN2);
   const int m0 = by * BM2;
   const int n0 = bx * BN2;
+  // ragged last N tile (N % 64 == 0, grid.x = ceil(N / BN2)): a dead wave
+  // skips fragment reads, MFMAs and stores but reaches every barrier
+  const bool live = BN2 > 64 ? ps_tr_wave_live(n0, wn, N) : true;
   int k_begin = 0, k_end = K;
   if (SPLITK) {
     k_begin = bz * kchunk;
@@ -836,12 +888,12 @@ void gemm_tn_tr_kernel(const __bf16* __restrict__ A,
   const bool ntb = SPLITK && gridDim.y == 1 && !GB2 &&
                    (int64_t)K * N * 2 > (192LL << 20);
   if (ntb)
-    stage_kmaj_tr<BN2, GB2, true>(b_lds[0], B, ldB, k_begin, n0, wid, lane,
-                                  &ga_b);
+    stage_panel_tr<BN2, GB2, true>(b_lds[0], B, ldB, k_begin, n0, N, wid,
+                                   lane, &ga_b);
   else
-    stage_kmaj_tr<BN2, GB2, false>(b_lds[0], B, ldB, k_begin, n0, wid, lane,
-                                   &ga_b);
-  stage_kmaj_tr<BM2>(a_lds[0], A, ldA, k_begin, m0, wid, lane);
+    stage_panel_tr<BN2, GB2, false>(b_lds[0], B, ldB, k_begin, n0, N, wid,
+                                    lane, &ga_b);
+  stage_panel_tr<BM2>(a_lds[0], A, ldA, k_begin, m0, M, wid, lane);
   __syncthreads();
   unsigned ab[2], bb[2];
 #pragma unroll
@@ -854,19 +906,21 @@ void gemm_tn_tr_kernel(const __bf16* __restrict__ A,
   int cur = 0;
   for (int k0 = k_begin; k0 < k_end; k0 += 64) {
     if (k0 + 64 < k_end) {
-      stage_kmaj_tr<BM2>(a_lds[cur ^ 1], A, ldA, k0 + 64, m0, wid, lane);
+      stage_panel_tr<BM2>(a_lds[cur ^ 1], A, ldA, k0 + 64, m0, M, wid,
+                          lane);
       if (ntb)
-        stage_kmaj_tr<BN2, GB2, true>(b_lds[cur ^ 1], B, ldB, k0 + 64, n0,
-                                      wid, lane, &ga_b);
+        stage_panel_tr<BN2, GB2, true>(b_lds[cur ^ 1], B, ldB, k0 + 64, n0,
+                                       N, wid, lane, &ga_b);
       else
-        stage_kmaj_tr<BN2, GB2, false>(b_lds[cur ^ 1], B, ldB, k0 + 64, n0,
-                                       wid, lane, &ga_b);
+        stage_panel_tr<BN2, GB2, false>(b_lds[cur ^ 1], B, ldB, k0 + 64, n0,
+                                        N, wid, lane, &ga_b);
     }
     // DEEP=2: both 32-k halves' transpose-reads go out before ONE wait,
     // doubling the MFMA burst per s_waitcnt (the 4-MFMA burst cannot hide
     // 8 ds_read_b64_tr latencies). Register cost doubles the fragment set,
     // so only tiles with FM2+FN2 <= 4 take it.
     constexpr int DEEP = (FM2 + FN2 <= 4) ? 2 : 1;
+    if (live) {
 #pragma unroll
     for (int kk = 0; kk < 64; kk += 32 * DEEP) {
       bf16x8 af[DEEP][FM2], bfr[DEEP][FN2];
@@ -874,12 +928,12 @@ void gemm_tn_tr_kernel(const __bf16* __restrict__ A,
       for (int d = 0; d < DEEP; ++d) {
 #pragma unroll
         for (int f = 0; f < FM2; ++f)
-          af[d][f] = tr_frag<BM2>(ab[cur], kk + d * 32 + q * 8, wm + f * 16,
-                                  l, BM2);
+          af[d][f] = tr_panel_frag<BM2>(ab[cur], kk + d * 32 + q * 8,
+                                        wm + f * 16, l);
 #pragma unroll
         for (int f = 0; f < FN2; ++f)
-          bfr[d][f] = tr_frag<BN2>(bb[cur], kk + d * 32 + q * 8, wn + f * 16,
-                                   l, BN2);
+          bfr[d][f] = tr_panel_frag<BN2>(bb[cur], kk + d * 32 + q * 8,
+                                         wn + f * 16, l);
       }
       tr_wait(af[0], bfr[0]);
       if (DEEP == 2) tr_wait(af[DEEP - 1], bfr[DEEP - 1]);
@@ -892,9 +946,11 @@ void gemm_tn_tr_kernel(const __bf16* __restrict__ A,
             acc[fm][fn] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
                 af[d][fm], bfr[d][fn], acc[fm][fn], 0, 0, 0);
     }
+    }
     __syncthreads();
     cur ^= 1;
   }
+  if (!live) return;  // past the last barrier
 #pragma unroll
   for (int fm = 0; fm < FM2; ++fm)
 #pragma unroll
@@ -925,30 +981,6 @@ struct GemmLaunch : GemmArgs {
 template <typename T, typename OUT>
 static void gemm_dispatch(const GemmLaunch& g, hipStream_t s);
 
-// Tile selection shared by the generic launcher (grid) and the split-K
-// plan. Cost model: MFMA time on the PADDED output plus LDS staging traffic
-// (each A panel is re-staged once per N-tile and vice versa). ALPHA ~= MACs
-// the matrix cores retire per element the memory system delivers (bf16:
-// ~1.25e15 MAC/s vs ~3.2e12 elem/s -> ~400).
-static void pick_gemm_tile(int M, int N, int* bm_out, int* bn_out) {
-  const int cand[6][2] = {{128, 128}, {128, 32}, {32, 128}, {64, 64},
-                          {128, 16},  {16, 128}};
-  const double ALPHA = 400.0;
-  double best = 0;
-  for (int i = 0; i < 6; ++i) {
-    int bm = cand[i][0], bn = cand[i][1];
-    int64_t tm = (M + bm - 1) / bm, tn = (N + bn - 1) / bn;
-    double flops = (double)(tm * bm) * (tn * bn) / ALPHA;  // (x K, common)
-    double staging = (double)tm * bm * tn + (double)tn * bn * tm;
-    double cost = flops + staging;
-    if (i == 0 || cost < best) {
-      best = cost;
-      *bm_out = bm;
-      *bn_out = bn;
-    }
-  }
-}
-
 // Atomic split-K adds into C, which the launcher zeroes as ONE contiguous
 // M*N block: only when nothing else lands in C and its rows are dense.
 static bool atomic_splitk_ok(const GemmArgs& g) {
@@ -956,14 +988,12 @@ static bool atomic_splitk_ok(const GemmArgs& g) {
          g.batch == 1 && g.ldc == g.N;
 }
 
-// Eligibility + shape plan for the tr16 TN path. Returns false if the
-// generic path must run; fills the interior [M0 x N0] (edge strips go
-// through the generic kernel), tile (bm, bn) and split-K for the interior.
-static bool tn_tr_plan(const GemmArgs& g, GemmPlan* p) {
+// Operand eligibility for the tr16 TN path: what ps_gemm_plan.h cannot see
+// from the shape alone (dtypes, layouts, alignment, epilogue).
+static bool tn_tr_operands_ok(const GemmArgs& g) {
   if (!g.in_bf16 || !g.out_f32) return false;
   if (g.a_klast || g.b_klast || g.gather_a) return false;
   if (g.bias || g.relu || g.beta != 0.0f || g.batch > 1) return false;
-  if (g.K % 64) return false;
   if (g.lda % 8) return false;
   if ((uintptr_t)g.A & 15) return false;
   if (g.gather_b) {
@@ -972,61 +1002,11 @@ static bool tn_tr_plan(const GemmArgs& g, GemmPlan* p) {
   } else {
     if (g.ldb % 8 || ((uintptr_t)g.B & 15)) return false;
   }
-  const int M0 = g.M & ~15, N0 = g.N & ~63;
-  if (M0 == 0 || N0 == 0) return false;
-  if (g.gather_b && (M0 != g.M || N0 != g.N)) return false;
-  if ((M0 != g.M || N0 != g.N) && (int64_t)M0 * N0 * g.K < (1LL << 33))
-    return false;
-  int bm = M0 % 64 ? (M0 % 32 ? 16 : 32) : 64;
-  int bn = (N0 % 128 == 0) ? 128 : 64;
-  if (N0 % bn) return false;
-  int64_t tiles = (int64_t)(M0 / bm) * (N0 / bn);
-  if (tiles >= 1024) return false;
-  int sk = 1, kchunk = g.K;
-  if (tiles < 384 && g.K >= 512 && atomic_splitk_ok(g)) {
-    int want = (int)((512 + tiles - 1) / tiles);
-    int maxsk = (g.K + 255) / 256;
-    sk = want < maxsk ? want : maxsk;
-    if (sk < 1) sk = 1;
-    kchunk = ((g.K / sk + 63) / 64) * 64;
-    // A-slice residency: tiles of one (by,bz) group share a bm x kchunk
-    // A slice via their XCD's 4 MiB L2 -- keep it under ~2 MiB so the
-    // NT-streamed B tiles have room to pass through without evicting it
-    const int kcap = ((2 << 20) / (bm * 2) / 64) * 64;
-    if (M0 == bm && kchunk > kcap && g.K > kcap) kchunk = kcap;
-    sk = (g.K + kchunk - 1) / kchunk;
-  }
-  *p = {true, sk, 0, M0, N0, bm, bn, kchunk};
   return true;
 }
 
-// Generic path: split K when the output tile grid cannot fill 256 CUs but
-// K is deep (conv wgrad: M=Cout, N=Kcol, K=N*OH*OW up to ~800k). 2
-// blocks/CU resident -> ~512 workgroups fill the chip; split K until the
-// grid gets there (wgrad at 512x4608 is 144 tiles = 28% occupancy without).
-static void generic_plan(const GemmArgs& g, GemmPlan* p) {
-  *p = {false, 1, 0, 0, 0, 0, 0, 0};
-  int tbm, tbn;
-  pick_gemm_tile(g.M, g.N, &tbm, &tbn);
-  const int64_t tiles =
-      (int64_t)((g.M + tbm - 1) / tbm) * ((g.N + tbn - 1) / tbn);
-  if (atomic_splitk_ok(g) && tiles < 384 && g.K >= 512) {
-    // atomic split-K: no workspace, so split much deeper (chunk >= 256)
-    // -- the un-split grid leaves most of the 256 CUs idle
-    int sk = (int)std::min<int64_t>((512 + tiles - 1) / tiles,
-                                    (g.K + 255) / 256);
-    if (sk > 1) p->splitk = sk;
-  } else if (g.batch == 1 && tiles < 384 && g.K >= 4096) {
-    // workspace split-K + reduce; cap the f32 workspace at 256 MB
-    int sk = (int)std::min<int64_t>((512 + tiles - 1) / tiles,
-                                    (g.K + 2047) / 2048);
-    int64_t ws_elems = (int64_t)sk * g.M * g.N;
-    if (sk > 1 && ws_elems * 4 <= (256LL << 20)) {
-      p->splitk = sk;
-      p->ws_elems = ws_elems;
-    }
-  }
-}
+// tests / tuning only (ps_gemm_set_tr_tune); all zero in the training path
+static TrTune g_tr_tune = {0, 0, 0};
 
 // Atomic split-K accumulates into C: zero it here, once, unless the caller
 // owns a buffer that the net-level zero_mt launch already zeroed this
@@ -1041,13 +1021,10 @@ static void run_gemm_tn_tr(const GemmArgs& g, const GemmPlan& p,
                            hipStream_t s) {
   const int M0 = p.M0, N0 = p.N0, bm = p.bm, bn = p.bn, sk = p.splitk;
   const int kchunk = p.kchunk;
-  int skz = sk;
-  if (sk > 1) {
-    const int nby = M0 / bm;
-    while (((int64_t)nby * skz) & 7) ++skz;  // pad: enables L2 clustering
-    zero_c_for_atomics(g, s);
-  }
-  dim3 grid(N0 / bn, M0 / bm, skz);
+  const int skz = ps_tr_grid_z(p);  // padded: enables L2 clustering
+  if (sk > 1) zero_c_for_atomics(g, s);
+  // ceil: a bn = 128 grid runs its last column tile ragged (N0 % 64 == 0)
+  dim3 grid((N0 + bn - 1) / bn, M0 / bm, skz);
   GatherDesc gb = g.gather_b ? *g.gather_b : GatherDesc{};
 #define PS_TR_LAUNCH(BM_, BN_, WGM_, WGN_)                                  \
   do {                                                                      \
@@ -1071,12 +1048,13 @@ static void run_gemm_tn_tr(const GemmArgs& g, const GemmPlan& p,
           (const __bf16*)g.A, (const __bf16*)g.B, (float*)g.C, M0, N0,      \
           g.K, g.lda, g.ldb, g.ldc, g.alpha, kchunk);                       \
   } while (0)
-  if (bm == 16 && bn == 128) PS_TR_LAUNCH(16, 128, 1, 4);
-  else if (bm == 16) PS_TR_LAUNCH(16, 64, 1, 4);
-  else if (bm == 32 && bn == 128) PS_TR_LAUNCH(32, 128, 1, 4);
-  else if (bm == 32) PS_TR_LAUNCH(32, 64, 1, 4);
-  else if (bn == 128) PS_TR_LAUNCH(64, 128, 2, 2);
-  else PS_TR_LAUNCH(64, 64, 2, 2);
+#define PS_TR_CASE(BM_, BN_, WGM_, WGN_) \
+  if (bm == BM_ && bn == BN_) PS_TR_LAUNCH(BM_, BN_, WGM_, WGN_); else
+  PS_TR_TILE_LIST(PS_TR_CASE) {
+    fprintf(stderr, "tr16 gemm: no %dx%d tile\n", bm, bn);
+    abort();
+  }
+#undef PS_TR_CASE
 #undef PS_TR_LAUNCH
   // edge strips [0,M) x [N0,N) and [M0,M) x [0,N0): generic kernel, unsplit
   // (plain stores over the zeroed C)
@@ -1211,7 +1189,13 @@ extern "C" {
 
 // tr16 plan first (bf16 in, fp32 out only), else the generic plan
 void ps_gemm_plan(const GemmArgs* g, GemmPlan* plan) {
-  if (!tn_tr_plan(*g, plan)) generic_plan(*g, plan);
+  const GemmShape sh = {g->M, g->N, g->K, g->batch, atomic_splitk_ok(*g),
+                        tn_tr_operands_ok(*g), g->gather_b != nullptr};
+  if (!ps_tn_tr_plan(sh, g_tr_tune, plan)) ps_generic_plan(sh, plan);
+}
+
+void ps_gemm_set_tr_tune(int bm, int bn, int target) {
+  g_tr_tune = {bm, bn, target};
 }
 
 // ws: plan->ws_elems floats (null when the plan asks for none)

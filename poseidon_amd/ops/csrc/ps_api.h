@@ -4,6 +4,7 @@
 #include <cstdint>
 
 #include "ps_conv_plan.h"  // ConvGeom, GatherDesc, ConvPlan
+#include "ps_gemm_plan.h"  // GemmPlan, TrTune
 
 struct GemmArgs {
   const void* A;
@@ -28,19 +29,6 @@ struct GemmArgs {
   bool c_prezeroed;
 };
 
-// How ps_gemm_run will execute a GemmArgs: made once by ps_gemm_plan, which
-// owns path choice and split-K policy. Split-K (small-tile huge-K GEMMs,
-// e.g. conv wgrad) either accumulates atomically into C -- the launcher
-// zeroes C itself unless c_prezeroed -- or, when ws_elems > 0, stores
-// partials into a caller-allocated f32 workspace of that many elements and
-// reduces. A workspace is only consumed by the path that sized it.
-struct GemmPlan {
-  bool tr16;         // bf16 TN ds_read_b64_tr_b16 path (else generic tiles)
-  int splitk;        // 1: no split
-  int64_t ws_elems;  // f32 workspace to pass to ps_gemm_run (0: none)
-  int M0, N0, bm, bn, kchunk;  // tr16 only: interior extent, tile, K slice
-};
-
 struct PoolGeom {
   int N, C, H, W, Ho, Wo;
   int kh, kw, sh, sw, ph, pw;
@@ -51,6 +39,8 @@ extern "C" {
 void ps_gemm_plan(const GemmArgs* g, GemmPlan* plan);
 void ps_gemm_run(const GemmArgs* g, const GemmPlan* plan, float* ws,
                  hipStream_t s);
+// tests / tuning: force the tr16 tile and split-K block target (0 = planner)
+void ps_gemm_set_tr_tune(int bm, int bn, int target);
 
 // elementwise.hip
 void ps_relu_fwd_f32(const float*, float*, int64_t, float, hipStream_t);
