@@ -246,6 +246,7 @@ class Net:
 
         self._fuse_relu_epilogues()
         self._fuse_relu_bwd_into_concats()
+        self._fuse_bwd_tails()
         for (li, ti, w) in self._loss_tops:
             self._loss_marks.setdefault(li, []).append((ti, w))
         # Loss layers whose loss top feeds NO consumer get the seeded weight
@@ -300,6 +301,105 @@ class Net:
                     relu.bwd_fused_into_consumer = True
             if mask_idx:
                 concat._mask_bottoms = mask_idx
+
+    def _fuse_bwd_tails(self) -> None:
+        """conv -> relu (in place) -> {lrn [-> max pool] | max pool | conv}:
+        the backward of the layer after the ReLU writes the conv's top diff,
+        so it also applies the ReLU mask and sums the conv's bias gradient
+        in the same pass (ops.lrn_backward_tail / pool_max_backward_tail /
+        relu_backward_bias). The ReLU's own backward, the pool's (under an
+        LRN) and the conv's bias colsum disappear: AlexNet's conv1/conv2
+        tails go from four memory-bound kernels over the conv output to one.
+        GPU, slope-0 in-place ReLUs behind a single-top, single-bottom conv
+        with a bias, vector-aligned channels, and a conv output of at least
+        PS_BWD_TAIL_MIN_BYTES (default 16 MiB: below that the block
+        reduction and atomics at the end of the fused kernel cost more than
+        the share of the batched colsum_mt launch they replace -- GoogLeNet's
+        21 small reduce convs lost 0.13 ms/step with it); everything else
+        keeps the per-layer path. PS_NO_BWD_TAIL_FUSION=1 disables (tests,
+        A/B runs); PS_MULTI_STREAM=1 also does (the bias gradient would be
+        written from the consumer's stream)."""
+        import os
+        if (ctx().device != "cuda" or os.environ.get("PS_NO_BWD_TAIL_FUSION")
+                or os.environ.get("PS_MULTI_STREAM", "0") == "1"):
+            return
+        p = self.param
+        bf16 = ctx().compute_dtype == torch.bfloat16
+        vecw = 8 if bf16 else 4
+        min_count = int(os.environ.get("PS_BWD_TAIL_MIN_BYTES", 16 << 20)) \
+            // (2 if bf16 else 4)
+
+        def sole_consumer(name: str, after: int):
+            """Index of the only layer reading blob `name` as produced by
+            layer `after` (None if several, or none)."""
+            found = None
+            for lj in range(after + 1, len(p.layers)):
+                if name in p.layers[lj].bottom:
+                    if found is not None:
+                        return None
+                    found = lj
+                if name in p.layers[lj].top and lj != found:
+                    break  # a later producer re-binds the name
+            return found
+
+        for li, lp in enumerate(p.layers):
+            relu = self.layers[li]
+            if (lp.enum_name("type") != "RELU" or len(lp.bottom) != 1
+                    or lp.top[0] != lp.bottom[0]
+                    or getattr(relu, "slope", 1.0) != 0.0
+                    or relu.loss_weights[0] != 0.0
+                    or getattr(relu, "bwd_fused_into_consumer", False)
+                    or not self.layer_need_bwd[li]
+                    or not self.bottom_need_bwd[li][0]):
+                continue
+            name = lp.bottom[0]
+            ci = next((lj for lj in range(li - 1, -1, -1)
+                       if name in p.layers[lj].top), None)
+            if ci is None or p.layers[ci].enum_name("type") != "CONVOLUTION":
+                continue
+            conv, clp = self.layers[ci], p.layers[ci]
+            if (len(clp.top) != 1 or len(clp.bottom) != 1
+                    or not conv.bias_term or conv.loss_weights[0] != 0.0
+                    or not self.layer_need_bwd[ci]
+                    or self.tops[ci][0].channels % vecw
+                    or self.tops[ci][0].count < min_count
+                    or any(ci < lj < li and name in p.layers[lj].bottom
+                           for lj in range(ci + 1, li))):
+                continue
+            ki = sole_consumer(name, li)
+            if ki is None or not self.layer_need_bwd[ki]:
+                continue
+            klp, cons = p.layers[ki], self.layers[ki]
+            if len(klp.bottom) != 1 or not self.bottom_need_bwd[ki][0]:
+                continue
+            ktype = klp.enum_name("type")
+            C = self.tops[ci][0].channels
+            if (ktype == "LRN" and cons.region == "ACROSS_CHANNELS"
+                    and cons.loss_weights[0] == 0.0
+                    and klp.top[0] != klp.bottom[0]
+                    and ops.lrn_v8_ok(C, cons.size)):
+                cons._tail_conv = conv
+                pi = sole_consumer(klp.top[0], ki)
+                if pi is not None:
+                    plp, pool = p.layers[pi], self.layers[pi]
+                    if (plp.enum_name("type") == "POOLING"
+                            and pool.method == "MAX" and len(plp.top) == 1
+                            and pool.loss_weights[0] == 0.0
+                            and self.layer_need_bwd[pi]
+                            and self.bottom_need_bwd[pi][0]):
+                        cons._tail_pool = pool
+                        cons._tail_pool_top = self.tops[pi][0]
+                        pool.bwd_fused_into_producer = True
+                relu.bwd_fused_into_consumer = True
+            elif (ktype == "POOLING" and cons.method == "MAX"
+                  and len(klp.top) == 1 and cons.loss_weights[0] == 0.0):
+                cons._tail_conv = conv
+                relu.bwd_fused_into_consumer = True
+            elif ktype == "CONVOLUTION":
+                relu._tail_conv = conv  # the ReLU's own backward sums db
+            else:
+                continue
+            conv.bias_grad_by_consumer = True
 
     def _build_stream_schedule(self, n_streams: int = 4) -> None:
         """Dataflow schedule for inter-branch stream parallelism.

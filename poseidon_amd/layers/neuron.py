@@ -29,6 +29,9 @@ class ReLULayer(NeuronLayer):
         rp = self.param.relu_param
         self.slope = float(rp.negative_slope) if rp is not None else 0.0
         self.fused = False  # producer GEMM applied the clamp in its epilogue
+        # Net's backward-tail pass (conv -> relu -> conv): our backward also
+        # sums this conv's bias gradient
+        self._tail_conv = None
 
     def forward(self, bottom, top) -> None:
         if self.fused:  # in-place: bottom[0] already holds relu(y)
@@ -38,8 +41,12 @@ class ReLULayer(NeuronLayer):
 
     def backward(self, top, propagate_down, bottom) -> None:
         if getattr(self, "bwd_fused_into_consumer", False):
-            return  # consumer CONCAT's split already applied the mask
-        if propagate_down[0]:
+            return  # the consumer's backward already applied the mask
+        if propagate_down[0] and self._tail_conv is not None:
+            bottom[0].diff = ops.relu_backward_bias(
+                bottom[0].data, top[0].diff,
+                self._tail_conv.blobs[1].diff.view(-1))
+        elif propagate_down[0]:
             # in-place safe: sign(bottom.data)==sign(x) after overwrite.
             # The GPU masks dy IN ITS OWN BUFFER (single-consumer DAG via
             # insert_splits): the diff tensor identity survives, so

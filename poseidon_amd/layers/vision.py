@@ -56,6 +56,9 @@ class ConvolutionLayer(Layer):
                                 # identities for downstream batching)
         self._pending_colsum = None  # (dy, db) for the net-level batch
         self._last_dy_ptr = None     # stability tracker for the batch
+        # Net's backward-tail pass: the layer that writes this conv's top
+        # diff also sums the bias gradient into blobs[1].diff
+        self.bias_grad_by_consumer = False
         channels = bottom[0].channels
         assert channels % self.group == 0 and self.num_output % self.group == 0
 
@@ -115,8 +118,9 @@ class ConvolutionLayer(Layer):
                    and dy.shape[1] % vecw == 0
                    and dy.is_contiguous(memory_format=torch.channels_last)
                    else None)
+            fused_db = self.bias_grad_by_consumer
             defer_db = (defer and self.bias_term and ptr is not None
-                        and ptr == self._last_dy_ptr)
+                        and ptr == self._last_dy_ptr and not fused_db)
             self._last_dy_ptr = ptr
             db = self.blobs[1].diff.view(-1) if self.bias_term else None
             cache = self._colT[i]
@@ -125,7 +129,7 @@ class ConvolutionLayer(Layer):
                 bo.data, colT, dy, self.blobs[0].diff, db,
                 self.stride, self.pad, self.group,
                 dwk_buf=self._dwk_cache if single else None,
-                skip_unpack=defer, skip_db=defer_db)
+                skip_unpack=defer, skip_db=defer_db or fused_db)
             if defer_db:
                 # bias grad joins the ONE net-level colsum_mt launch
                 self._pending_colsum = (dy, db)
@@ -184,6 +188,9 @@ class PoolingLayer(Layer):
         if self.method != "AVE":
             assert self.pad == (0, 0) or self.method == "MAX"
         self._mask = None
+        # Net's backward-tail pass (conv -> relu -> [lrn] -> this MAX pool):
+        self.bwd_fused_into_producer = False  # the LRN below gathers for us
+        self._tail_conv = None  # conv whose ReLU mask and bias sum we apply
 
     def reshape(self, bottom, top) -> None:
         n, c, h, w = bottom[0].shape
@@ -229,9 +236,19 @@ class PoolingLayer(Layer):
         return h * W + w
 
     def backward(self, top, propagate_down, bottom) -> None:
-        if not propagate_down[0]:
+        if not propagate_down[0] or self.bwd_fused_into_producer:
             return
         dy = top[0].diff
+        if self._tail_conv is not None:
+            dx = ops.pool_max_backward_tail(
+                dy, self._mask, bottom[0].data, self.kernel, self.stride,
+                self.pad, db=self._tail_conv.blobs[1].diff.view(-1),
+                dx_out=getattr(self, "_dx_cache", None))
+            cur = getattr(self, "_dx_cache", None)
+            if cur is None or cur.data_ptr() != dx.data_ptr():
+                self._dx_cache = dx
+            bottom[0].diff = self._dx_cache
+            return
         if self.method == "AVE":
             bottom[0].diff = ops.pool_ave_backward(
                 dy, bottom[0].shape, self.kernel, self.stride, self.pad)
@@ -262,6 +279,11 @@ class LRNLayer(Layer):
         self.region = lp.enum_name("norm_region")
         self._scale = None
         self._y = None
+        # Net's backward-tail pass (conv -> relu -> this LRN [-> max pool])
+        self._tail_conv = None  # conv whose ReLU mask and bias sum we apply
+        self._tail_pool = None  # consumer pool whose backward we gather
+        self._tail_pool_top = None  # ... and its top blob (we read the diff)
+        self._dx_cache = None
         if self.region == "WITHIN_CHANNEL":
             # composite: x^2 -> ave-pool(size) -> scale -> x * scale^-beta
             self.pre_pad = (self.size - 1) // 2
@@ -287,7 +309,21 @@ class LRNLayer(Layer):
         if not propagate_down[0]:
             return
         x, dy = bottom[0].data, top[0].diff
-        if self.region == "ACROSS_CHANNELS":
+        if self._tail_conv is not None:
+            pool = self._tail_pool
+            if pool is not None:
+                dy = self._tail_pool_top.diff
+            dx = ops.lrn_backward_tail(
+                x, self._y, dy, self.size, self.alpha, self.beta, relu=True,
+                db=self._tail_conv.blobs[1].diff.view(-1),
+                pool=None if pool is None else (pool._mask, pool.kernel,
+                                                pool.stride, pool.pad),
+                dx_out=self._dx_cache)
+            if (self._dx_cache is None
+                    or self._dx_cache.data_ptr() != dx.data_ptr()):
+                self._dx_cache = dx
+            bottom[0].diff = self._dx_cache
+        elif self.region == "ACROSS_CHANNELS":
             bottom[0].diff = ops.lrn_backward(x, self._y, self._scale, dy,
                                               self.size, self.alpha, self.beta)
         else:

@@ -861,6 +861,123 @@ Tensor lrn_backward(const Tensor& x, const Tensor& y, const Tensor& scale,
 }
 
 // ---------------------------------------------------------------------------
+// Fused backward tails of a conv block (conv -> relu -> [lrn] -> [max pool]):
+// one pass over the conv output writes dx, already masked by the in-place
+// ReLU, and adds its column sum into the conv's fp32 bias gradient.
+// ---------------------------------------------------------------------------
+
+// Block caps of the launches that end in a bias flush. Every block issues C
+// global atomics when it retires, so past the point where the chip is busy
+// more blocks only add atomic traffic: the cap is an atomics budget over C,
+// clamped to a per-kernel range (measured sweeps:
+// profiles/bwd_tail_fusion.md). The LRN tail is latency-bound and wants
+// two rounds of its 4 resident blocks per CU; the flat pool and ReLU tails
+// stream and do with 1-2 blocks per CU once C is large.
+int clampi(int v, int lo, int hi) { return v < lo ? lo : v > hi ? hi : v; }
+int lrn_tail_blocks(int C) { return clampi((512 << 10) / C, 1024, 2048); }
+int pool_tail_blocks(int C) { return clampi((128 << 10) / C, 256, 2048); }
+int relu_tail_blocks(int C) { return clampi((64 << 10) / C, 256, 1024); }
+// 0 = the rules above; tests lower it to force grid striding
+std::atomic<int> g_tail_blocks{0};
+void set_bwd_tail_blocks(int64_t n) { g_tail_blocks = n > 0 ? (int)n : 0; }
+int tail_blocks(int dflt) {
+  const int n = g_tail_blocks.load();
+  return n > 0 ? n : dflt;
+}
+
+float* tail_db(const c10::optional<Tensor>& db, int C) {
+  if (!db.has_value()) return nullptr;
+  TORCH_CHECK(db->is_cuda() && db->scalar_type() == at::kFloat &&
+              db->is_contiguous() && db->numel() == C,
+              "bias gradient: contiguous f32 device tensor of C elements");
+  return db->data_ptr<float>();
+}
+
+// LRN backward on the vec8 path. pool_mask given: dy is the top diff of the
+// max pool that consumes this LRN's output (mask and geometry are that
+// pool's) and the pool's own backward is skipped. relu: x is a post-ReLU
+// conv output, dx is masked by x > 0. db: += column sum of dx.
+Tensor lrn_backward_tail(const Tensor& x, const Tensor& y, const Tensor& dy,
+                         int size, double alpha, double beta, bool relu,
+                         const c10::optional<Tensor>& db,
+                         const c10::optional<Tensor>& pool_mask, int kh,
+                         int kw, int sh, int sw, int ph, int pw,
+                         const c10::optional<Tensor>& dx_out) {
+  auto x_cl = cl4(x);
+  auto y_cl = cl4(y);
+  auto dy_cl = cl4(dy);
+  int64_t rows = (int64_t)x_cl.size(0) * x_cl.size(2) * x_cl.size(3);
+  int C = x_cl.size(1);
+  TORCH_CHECK(ps_lrn_v8_ok(C, size), "lrn tail: needs the vec8 LRN path");
+  TORCH_CHECK(y.sizes() == x.sizes() && y.scalar_type() == x.scalar_type() &&
+              dy.scalar_type() == x.scalar_type());
+  TORCH_CHECK(rows < (int64_t)1 << 31, "lrn tail: rows exceed 32 bits");
+  Tensor dx = reuse_or_empty_cl(dx_out, x.sizes(), x);
+  PoolGeom g{};
+  Tensor mask_cl;
+  const uint8_t* mask = nullptr;
+  if (pool_mask.has_value()) {
+    mask_cl = cl4(*pool_mask);
+    TORCH_CHECK(mask_cl.scalar_type() == at::kByte &&
+                mask_cl.sizes() == dy.sizes(), "lrn tail: u8 mask like dy");
+    g = pool_geom_bwd(x.sizes().vec(), dy_cl, kh, kw, sh, sw, ph, pw);
+    TORCH_CHECK(dy_cl.size(0) == g.N && dy_cl.size(1) == g.C &&
+                g.Ho == pool_out(g.H, kh, ph, sh) &&
+                g.Wo == pool_out(g.W, kw, pw, sw),
+                "lrn tail: pool top diff does not match the geometry");
+    mask = mask_cl.data_ptr<uint8_t>();
+  } else {
+    TORCH_CHECK(dy.sizes() == x.sizes());
+  }
+  PS_CALL(lrn_bwd_v8_tail, is_bf16(x), P(x_cl), P(y_cl), P(dy_cl), mask, &g,
+          P(dx), tail_db(db, C), relu ? 1 : 0, rows, C, size, (float)alpha,
+          (float)beta, tail_blocks(lrn_tail_blocks(C)), stream());
+  return dx;
+}
+
+// max-pool backward whose bottom is a post-ReLU conv output x: dx masked by
+// x > 0, db += column sum of dx
+Tensor pool_max_backward_tail(const Tensor& dy, const Tensor& mask,
+                              const Tensor& x, int kh, int kw, int sh, int sw,
+                              int ph, int pw, const c10::optional<Tensor>& db,
+                              const c10::optional<Tensor>& dx_out) {
+  auto dy_cl = cl4(dy);
+  auto mask_cl = cl4(mask);
+  auto x_cl = cl4(x);
+  PoolGeom g = pool_geom_bwd(x.sizes().vec(), dy_cl, kh, kw, sh, sw, ph, pw);
+  TORCH_CHECK(g.C % (is_bf16(dy) ? 8 : 4) == 0,
+              "pool tail: channels must fill whole vectors");
+  TORCH_CHECK(x.scalar_type() == dy.scalar_type() &&
+              mask_cl.scalar_type() == at::kByte &&
+              mask_cl.sizes() == dy.sizes() && dy_cl.size(0) == g.N &&
+              dy_cl.size(1) == g.C && g.Ho == pool_out(g.H, kh, ph, sh) &&
+              g.Wo == pool_out(g.W, kw, pw, sw) && g.C * 4 <= 64 * 1024,
+              "pool tail: operands do not match the geometry");
+  Tensor dx = reuse_or_empty_cl(dx_out, x.sizes(), dy);
+  PS_CALL(maxpool_bwd_tail, is_bf16(dy), P(dy_cl), mask_cl.data_ptr<uint8_t>(),
+          P(x_cl), P(dx), tail_db(db, g.C), &g, tail_blocks(pool_tail_blocks(g.C)),
+          stream());
+  return dx;
+}
+
+// in-place slope-0 ReLU backward of a channels-last 4D (or [rows, C]) dy
+// + db += column sum of dx
+Tensor relu_backward_bias(const Tensor& x, Tensor dy, Tensor db) {
+  int64_t rows;
+  int C;
+  Tensor xc = as_rows(x, &rows, &C);
+  Tensor dyc = as_rows(dy, &rows, &C);
+  TORCH_CHECK(dyc.data_ptr() == dy.data_ptr(),
+              "relu_backward_bias: dy must be dense in its row layout");
+  TORCH_CHECK(x.sizes() == dy.sizes() && x.scalar_type() == dy.scalar_type() &&
+              C % (is_bf16(x) ? 8 : 4) == 0 && C * 4 <= 64 * 1024,
+              "relu_backward_bias: mismatched operands or unaligned channels");
+  PS_CALL(relu_bwd_bias, is_bf16(x), P(xc), P(dyc), P(dyc), tail_db(db, C),
+          rows, C, tail_blocks(relu_tail_blocks(C)), stream());
+  return dy;
+}
+
+// ---------------------------------------------------------------------------
 // Softmax family
 // ---------------------------------------------------------------------------
 
@@ -1328,6 +1445,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("pool_stoch_forward_test", &pool_stoch_forward_test);
   m.def("lrn_forward", &lrn_forward);
   m.def("lrn_backward", &lrn_backward);
+  m.def("lrn_backward_tail", &lrn_backward_tail);
+  m.def("pool_max_backward_tail", &pool_max_backward_tail);
+  m.def("relu_backward_bias", &relu_backward_bias);
+  m.def("set_bwd_tail_blocks", &set_bwd_tail_blocks);
+  m.def("lrn_v8_ok", &ps_lrn_v8_ok);
   m.def("softmax_forward", &softmax_forward);
   m.def("softmax_backward", &softmax_backward);
   m.def("softmax_loss_forward", &softmax_loss_forward);

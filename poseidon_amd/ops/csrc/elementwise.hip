@@ -5,6 +5,7 @@
 
 #include "ps_common.h"
 #include "ps_mt.h"
+#include "ps_bwd_tail.h"
 
 namespace ps {
 
@@ -61,6 +62,36 @@ __global__ void relu_bwd_v8_k(const __bf16* __restrict__ x,
     }
     ((bf16x8*)dx)[i] = o;
   }
+}
+
+// relu -> conv tail: slope-0 ReLU backward over [rows][C] that also adds
+// the column sum of the stored dx into db, the bias gradient of the conv
+// below the ReLU. Launched with bias_flat_blocks (a thread keeps its channel
+// chunk) and C floats of dynamic LDS; dx may alias dy.
+template <typename T, int V>
+__global__ void relu_bwd_bias_k(const T* x, const T* dy, T* dx, float* db,
+                                int64_t nvec, int C) {
+  typedef T vec_t __attribute__((ext_vector_type(V)));
+  extern __shared__ float part[];  // C floats
+  int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int c0 = (int)(i % (C / V)) * V;
+  float bacc[V];
+#pragma unroll
+  for (int e = 0; e < V; ++e) bacc[e] = 0.f;
+  bias_sum_init(part, C);
+  for (; i < nvec; i += (int64_t)gridDim.x * blockDim.x) {
+    vec_t xv = ((const vec_t*)x)[i], dyv = ((const vec_t*)dy)[i], o;
+#pragma unroll
+    for (int e = 0; e < V; ++e) {
+      const float g = relu_mask(to_f32(xv[e]), to_f32(dyv[e]));
+      T r;
+      from_f32(g, r);
+      o[e] = r;
+      bacc[e] += g;
+    }
+    ((vec_t*)dx)[i] = o;
+  }
+  bias_sum_flush<V>(part, bacc, c0, true, db, C);
 }
 
 template <typename T>
@@ -462,6 +493,22 @@ void ps_relu_bwd_bf16(const void* x, const void* dy, void* dx, int64_t n,
   else
     PS_EW_LAUNCH(relu_bwd_k<__bf16>, (const __bf16*)x, (const __bf16*)dy,
                  (__bf16*)dx, n, slope);
+}
+// slope-0 ReLU backward + db += colsum(dx); C % 4 (f32) / C % 8 (bf16) == 0
+void ps_relu_bwd_bias_f32(const float* x, const float* dy, float* dx,
+                          float* db, int64_t rows, int C, int max_blocks,
+                          hipStream_t s) {
+  const int64_t nvec = rows * C / 4;
+  relu_bwd_bias_k<float, 4><<<dim3(bias_flat_blocks(nvec, C / 4, max_blocks)),
+                              256, C * 4, s>>>(x, dy, dx, db, nvec, C);
+}
+void ps_relu_bwd_bias_bf16(const void* x, const void* dy, void* dx, float* db,
+                           int64_t rows, int C, int max_blocks,
+                           hipStream_t s) {
+  const int64_t nvec = rows * C / 8;
+  relu_bwd_bias_k<__bf16, 8><<<dim3(bias_flat_blocks(nvec, C / 8, max_blocks)),
+                               256, C * 4, s>>>(
+      (const __bf16*)x, (const __bf16*)dy, (__bf16*)dx, db, nvec, C);
 }
 
 void ps_dropout_fwd_f32(const float* x, float* y, uint8_t* mask, int64_t n,

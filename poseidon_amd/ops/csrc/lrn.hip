@@ -9,6 +9,7 @@
 //             - (2*alpha*beta/size) * x_i * sum_{j in window(i)} dy_j*y_j/scale_j
 
 #include "ps_common.h"
+#include "ps_bwd_tail.h"
 
 namespace ps {
 
@@ -203,14 +204,31 @@ template <> struct LrnV8<__bf16> {
   }
 };
 
+// Thread mapping of the v8 kernels: the halos travel by one-lane wave
+// shuffles, so a pixel row (gpr = C/8 lanes) must never straddle two waves.
+// Each wave takes 64 / gpr WHOLE rows and idles its spare lanes; a 256-thread
+// block covers rpb = 4 * (64 / gpr) rows.
+struct LrnV8Map {
+  int lr, lg;
+  bool active;
+  __device__ LrnV8Map(int gpr) {
+    const int lane = threadIdx.x & (kWave - 1);
+    const int rpw = kWave / gpr;
+    const int wr = lane / gpr;  // once per thread
+    lg = lane - wr * gpr;
+    active = wr < rpw;
+    lr = (threadIdx.x / kWave) * rpw + wr;
+  }
+};
+
 template <typename T, int PRE>
 __global__ void lrn_fwd_v8_k(const T* __restrict__ x, T* __restrict__ y,
                              int64_t rows, int C, float alpha_over_n,
                              float beta, int gpr, int rpb) {
-  const int t = threadIdx.x;
-  const int lr = t / gpr, lg = t - lr * gpr;  // once per thread
+  const LrnV8Map map(gpr);
+  const int lr = map.lr, lg = map.lg;
   const int cb = lg * 8;
-  const bool active = lr < rpb;
+  const bool active = map.active;
   for (int64_t r0 = (int64_t)blockIdx.x * rpb; r0 < rows;
        r0 += (int64_t)gridDim.x * rpb) {
     const int64_t row = r0 + lr;
@@ -254,15 +272,98 @@ __global__ void lrn_fwd_v8_k(const T* __restrict__ x, T* __restrict__ y,
   }
 }
 
-template <typename T, int PRE>
-__global__ void lrn_bwd_v8_k(const T* __restrict__ x, const T* __restrict__ y,
-                             const T* __restrict__ dy, T* __restrict__ dx,
-                             int64_t rows, int C, float alpha_over_n,
-                             float cache_ratio, float beta, int gpr, int rpb) {
-  const int t = threadIdx.x;
-  const int lr = t / gpr, lg = t - lr * gpr;
+// The LRN backward arithmetic of one thread's 8 channels, shared by every
+// instantiation of lrn_bwd_v8_k so that fused and unfused results agree to
+// the bit. Shuffles inside: the whole wave calls it (idle and out-of-range
+// lanes with zeros).
+template <int PRE>
+__device__ __forceinline__ void lrn_bwd_v8_math(const float* xv,
+                                                const float* yv,
+                                                const float* dyv, int lg,
+                                                int gpr, float alpha_over_n,
+                                                float cache_ratio, float beta,
+                                                float* out) {
+  float sq[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) sq[j] = xv[j] * xv[j];
+  // x^2 halo reaches 2P (scale of the halo ratio positions), y/dy halo P
+  float lhx[2 * PRE], rhx[2 * PRE], lhy[PRE], rhy[PRE], lhd[PRE], rhd[PRE];
+#pragma unroll
+  for (int j = 0; j < 2 * PRE; ++j) {
+    lhx[j] = __shfl_up(sq[8 - 2 * PRE + j], 1);
+    rhx[j] = __shfl_down(sq[j], 1);
+  }
+#pragma unroll
+  for (int j = 0; j < PRE; ++j) {
+    lhy[j] = __shfl_up(yv[8 - PRE + j], 1);
+    rhy[j] = __shfl_down(yv[j], 1);
+    lhd[j] = __shfl_up(dyv[8 - PRE + j], 1);
+    rhd[j] = __shfl_down(dyv[j], 1);
+  }
+  if (lg == 0) {
+#pragma unroll
+    for (int j = 0; j < 2 * PRE; ++j) lhx[j] = 0.f;
+#pragma unroll
+    for (int j = 0; j < PRE; ++j) lhy[j] = lhd[j] = 0.f;
+  }
+  if (lg == gpr - 1) {
+#pragma unroll
+    for (int j = 0; j < 2 * PRE; ++j) rhx[j] = 0.f;
+#pragma unroll
+    for (int j = 0; j < PRE; ++j) rhy[j] = rhd[j] = 0.f;
+  }
+  // xs-space index m in [-2P, 8+2P) -> value
+  auto XS = [&](int m) {
+    return (m < 0) ? lhx[m + 2 * PRE]
+                   : (m < 8) ? sq[m] : rhx[m - 8];
+  };
+  // scale at positions [-P, 8+P), ratio = dy*y/scale there
+  float ratio[8 + 2 * PRE], scc[8];
+#pragma unroll
+  for (int i2 = 0; i2 < 8 + 2 * PRE; ++i2) {
+    const int m = i2 - PRE;
+    float ss = 0.f;
+#pragma unroll
+    for (int k = -PRE; k <= PRE; ++k) ss += XS(m + k);
+    const float sc = 1.0f + alpha_over_n * ss;
+    const float r = rsqrtf(sc);
+    if (m >= 0 && m < 8) scc[m] = sc;
+    const float ym = (m < 0) ? lhy[m + PRE] : (m < 8) ? yv[m] : rhy[m - 8];
+    const float dm = (m < 0) ? lhd[m + PRE] : (m < 8) ? dyv[m] : rhd[m - 8];
+    ratio[i2] = dm * ym * (r * r);  // 1/sc via rsqrt^2 (no v_div chain)
+  }
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    float acc = 0.f;
+#pragma unroll
+    for (int k = 0; k <= 2 * PRE; ++k) acc += ratio[j + k];
+    out[j] = dyv[j] * lrn_pow_negbeta(scc[j], beta)
+             - cache_ratio * xv[j] * acc;
+  }
+}
+
+// Backward, optionally fused with its neighbours in a conv block
+// (conv -> relu -> lrn -> max pool):
+//   POOL  dy is not read: it is gathered from the pool's top diff and u8
+//         mask (dy = dpool, g = the pool's geometry; its input is this
+//         LRN's output), rounded to T as maxpool_bwd_k would have stored it
+//   RELU  x is the post-ReLU conv output: dx (rounded to T) is masked by
+//         x > 0, as the in-place relu_bwd that followed did
+//   BIAS  db[c] += column sum of the stored dx (the conv's bias gradient)
+template <typename T, int PRE, bool POOL, bool RELU, bool BIAS>
+__global__ void __launch_bounds__(256)
+lrn_bwd_v8_k(const T* __restrict__ x, const T* __restrict__ y,
+             const T* __restrict__ dy, const uint8_t* __restrict__ mask,
+             PoolGeom g, T* __restrict__ dx, float* __restrict__ db,
+             int64_t rows, int C, float alpha_over_n, float cache_ratio,
+             float beta, int gpr, int rpb) {
+  __shared__ float part[BIAS ? 512 : 1];  // gpr <= 64: C <= 512
+  const LrnV8Map map(gpr);
+  const int lr = map.lr, lg = map.lg;
   const int cb = lg * 8;
-  const bool active = lr < rpb;
+  const bool active = map.active;
+  float bacc[8] = {};
+  if (BIAS) bias_sum_init(part, C);
   for (int64_t r0 = (int64_t)blockIdx.x * rpb; r0 < rows;
        r0 += (int64_t)gridDim.x * rpb) {
     const int64_t row = r0 + lr;
@@ -272,91 +373,108 @@ __global__ void lrn_bwd_v8_k(const T* __restrict__ x, const T* __restrict__ y,
     if (ok) {
       LrnV8<T>::load8(x + base, xv);
       LrnV8<T>::load8(y + base, yv);
-      LrnV8<T>::load8(dy + base, dyv);
-    }
-    float sq[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) sq[j] = xv[j] * xv[j];
-    // x^2 halo reaches 2P (scale of the halo ratio positions), y/dy halo P
-    float lhx[2 * PRE], rhx[2 * PRE], lhy[PRE], rhy[PRE], lhd[PRE], rhd[PRE];
-#pragma unroll
-    for (int j = 0; j < 2 * PRE; ++j) {
-      lhx[j] = __shfl_up(sq[8 - 2 * PRE + j], 1);
-      rhx[j] = __shfl_down(sq[j], 1);
-    }
-#pragma unroll
-    for (int j = 0; j < PRE; ++j) {
-      lhy[j] = __shfl_up(yv[8 - PRE + j], 1);
-      rhy[j] = __shfl_down(yv[j], 1);
-      lhd[j] = __shfl_up(dyv[8 - PRE + j], 1);
-      rhd[j] = __shfl_down(dyv[j], 1);
-    }
-    if (lg == 0) {
-#pragma unroll
-      for (int j = 0; j < 2 * PRE; ++j) lhx[j] = 0.f;
-#pragma unroll
-      for (int j = 0; j < PRE; ++j) lhy[j] = lhd[j] = 0.f;
-    }
-    if (lg == gpr - 1) {
-#pragma unroll
-      for (int j = 0; j < 2 * PRE; ++j) rhx[j] = 0.f;
-#pragma unroll
-      for (int j = 0; j < PRE; ++j) rhy[j] = rhd[j] = 0.f;
-    }
-    if (!ok) continue;
-    // xs-space index m in [-2P, 8+2P) -> value
-    auto XS = [&](int m) {
-      return (m < 0) ? lhx[m + 2 * PRE]
-                     : (m < 8) ? sq[m] : rhx[m - 8];
-    };
-    // scale at positions [-P, 8+P), ratio = dy*y/scale there
-    float ratio[8 + 2 * PRE], scc[8];
-#pragma unroll
-    for (int i2 = 0; i2 < 8 + 2 * PRE; ++i2) {
-      const int m = i2 - PRE;
-      float ss = 0.f;
-#pragma unroll
-      for (int k = -PRE; k <= PRE; ++k) ss += XS(m + k);
-      const float sc = 1.0f + alpha_over_n * ss;
-      const float r = rsqrtf(sc);
-      if (m >= 0 && m < 8) scc[m] = sc;
-      const float ym = (m < 0) ? lhy[m + PRE] : (m < 8) ? yv[m] : rhy[m - 8];
-      const float dm = (m < 0) ? lhd[m + PRE] : (m < 8) ? dyv[m] : rhd[m - 8];
-      ratio[i2] = dm * ym * (r * r);  // 1/sc via rsqrt^2 (no v_div chain)
+      if (POOL) {
+        // rows = N*H*W fits 32 bits (checked by the launcher)
+        const unsigned r = (unsigned)row;
+        const unsigned q = r / (unsigned)g.W;
+        const int w = (int)(r - q * (unsigned)g.W);
+        const int n = (int)(q / (unsigned)g.H);
+        const int h = (int)(q - (unsigned)n * (unsigned)g.H);
+        maxpool_gather<T, 8>(dy, mask, g, n, h, w, cb, dyv);
+      } else {
+        LrnV8<T>::load8(dy + base, dyv);
+      }
     }
     float out[8];
+    lrn_bwd_v8_math<PRE>(xv, yv, dyv, lg, gpr, alpha_over_n, cache_ratio,
+                         beta, out);
+    if (!ok) continue;
+    if (RELU || BIAS) {
 #pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      float acc = 0.f;
-#pragma unroll
-      for (int k = 0; k <= 2 * PRE; ++k) acc += ratio[j + k];
-      out[j] = dyv[j] * lrn_pow_negbeta(scc[j], beta)
-               - cache_ratio * xv[j] * acc;
+      for (int j = 0; j < 8; ++j) {
+        T o;
+        from_f32(out[j], o);
+        out[j] = to_f32(o);
+        if (RELU) out[j] = relu_mask(xv[j], out[j]);
+        if (BIAS) bacc[j] += out[j];
+      }
     }
-    LrnV8<T>::store8(dx + row * C + cb, out);
+    LrnV8<T>::store8(dx + base, out);
   }
+  if (BIAS) bias_sum_flush<8>(part, bacc, cb, active, db, C);
 }
 
 template <typename T>
 static bool lrn_v8_ok(int C, int size) {
   const int pre = (size - 1) / 2;
   // pre <= 2: the shfl halo reaches one neighbor lane (8 channels); wider
-  // windows fall back to the LDS row-block kernels
-  return (C % 8 == 0) && C >= 8 && (C / 8) <= 256 && (size % 2 == 1) &&
+  // windows fall back to the LDS row-block kernels. gpr <= 64: a row's
+  // lanes sit in one wave.
+  return (C % 8 == 0) && C >= 8 && (C / 8) <= kWave && (size % 2 == 1) &&
          pre >= 1 && pre <= 2;
 }
 
+#define LRN_V8_GEOM                                                       \
+  const int pre_ = (size - 1) / 2;                                        \
+  const int gpr_ = C / 8;                                                 \
+  const int rpb_ = 4 * (kWave / gpr_)
+
 #define LRN_V8_DISPATCH(kernel, T, ...)                                   \
   do {                                                                    \
-    const int pre_ = (size - 1) / 2;                                      \
-    const int gpr_ = C / 8;                                               \
-    const int rpb_ = 256 / gpr_;                                          \
+    LRN_V8_GEOM;                                                          \
     dim3 grid_ = lrn_grid(rows, rpb_);                                    \
     switch (pre_) {                                                       \
       case 1: kernel<T, 1><<<grid_, 256, 0, s>>>(__VA_ARGS__, gpr_, rpb_); break; \
       default: kernel<T, 2><<<grid_, 256, 0, s>>>(__VA_ARGS__, gpr_, rpb_); break; \
     }                                                                     \
   } while (0)
+
+template <typename T, int PRE, bool POOL, bool RELU>
+static void lrn_bwd_v8_launch(const T* x, const T* y, const T* dy,
+                              const uint8_t* mask, const PoolGeom& g, T* dx,
+                              float* db, int64_t rows, int C, float an,
+                              float cr, float beta, int gpr, int rpb,
+                              int max_blocks, hipStream_t s) {
+  if (db) {
+    // every block ends in C global atomics: a few resident blocks per CU
+    // stride over the rows, not one block per row group
+    int64_t blocks = cdiv64(rows, rpb);
+    if (blocks > max_blocks) blocks = max_blocks;
+    lrn_bwd_v8_k<T, PRE, POOL, RELU, true><<<dim3((unsigned)blocks), 256, 0, s>>>(
+        x, y, dy, mask, g, dx, db, rows, C, an, cr, beta, gpr, rpb);
+  } else {
+    lrn_bwd_v8_k<T, PRE, POOL, RELU, false><<<lrn_grid(rows, rpb), 256, 0, s>>>(
+        x, y, dy, mask, g, dx, db, rows, C, an, cr, beta, gpr, rpb);
+  }
+}
+
+// mask/g null: plain dy. db null: no bias sum.
+template <typename T>
+static void lrn_bwd_v8_any(const T* x, const T* y, const T* dy,
+                           const uint8_t* mask, const PoolGeom* g, T* dx,
+                           float* db, bool relu, int64_t rows, int C, int size,
+                           float alpha, float beta, int max_blocks,
+                           hipStream_t s) {
+  const float an = alpha / size;
+  const float cr = 2.0f * alpha * beta / size;
+  LRN_V8_GEOM;
+  const bool pool = mask != nullptr;
+  const PoolGeom gg = pool ? *g : PoolGeom{};
+#define LRN_BWD_CASE(P, PL, RL)                                           \
+  if (pre_ == P && pool == PL && relu == RL)                              \
+    return lrn_bwd_v8_launch<T, P, PL, RL>(x, y, dy, mask, gg, dx, db,    \
+                                           rows, C, an, cr, beta, gpr_,   \
+                                           rpb_, max_blocks, s)
+  LRN_BWD_CASE(1, false, false);
+  LRN_BWD_CASE(1, false, true);
+  LRN_BWD_CASE(1, true, false);
+  LRN_BWD_CASE(1, true, true);
+  LRN_BWD_CASE(2, false, false);
+  LRN_BWD_CASE(2, false, true);
+  LRN_BWD_CASE(2, true, false);
+  LRN_BWD_CASE(2, true, true);
+#undef LRN_BWD_CASE
+}
 
 extern "C" {
 
@@ -376,17 +494,34 @@ void ps_lrn_fwd_v8_bf16(const void* x, void* y, int64_t rows, int C,
 void ps_lrn_bwd_v8_f32(const float* x, const float* y, const float* dy,
                        float* dx, int64_t rows, int C, int size, float alpha,
                        float beta, hipStream_t s) {
-  const float an = alpha / size;
-  const float cr = 2.0f * alpha * beta / size;
-  LRN_V8_DISPATCH(lrn_bwd_v8_k, float, x, y, dy, dx, rows, C, an, cr, beta);
+  lrn_bwd_v8_any<float>(x, y, dy, nullptr, nullptr, dx, nullptr, false, rows,
+                        C, size, alpha, beta, 0, s);
 }
 void ps_lrn_bwd_v8_bf16(const void* x, const void* y, const void* dy,
                         void* dx, int64_t rows, int C, int size, float alpha,
                         float beta, hipStream_t s) {
-  const float an = alpha / size;
-  const float cr = 2.0f * alpha * beta / size;
-  LRN_V8_DISPATCH(lrn_bwd_v8_k, __bf16, (const __bf16*)x, (const __bf16*)y,
-                  (const __bf16*)dy, (__bf16*)dx, rows, C, an, cr, beta);
+  lrn_bwd_v8_any<__bf16>((const __bf16*)x, (const __bf16*)y, (const __bf16*)dy,
+                         nullptr, nullptr, (__bf16*)dx, nullptr, false, rows,
+                         C, size, alpha, beta, 0, s);
+}
+// fused tail: dy is the pool's top diff when mask/g are given (else this
+// layer's own top diff); relu masks dx by x > 0; db (may be null) += colsum
+void ps_lrn_bwd_v8_tail_f32(const float* x, const float* y, const float* dy,
+                            const uint8_t* mask, const PoolGeom* g, float* dx,
+                            float* db, int relu, int64_t rows, int C, int size,
+                            float alpha, float beta, int max_blocks,
+                            hipStream_t s) {
+  lrn_bwd_v8_any<float>(x, y, dy, mask, g, dx, db, relu != 0, rows, C, size,
+                        alpha, beta, max_blocks, s);
+}
+void ps_lrn_bwd_v8_tail_bf16(const void* x, const void* y, const void* dy,
+                             const uint8_t* mask, const PoolGeom* g, void* dx,
+                             float* db, int relu, int64_t rows, int C,
+                             int size, float alpha, float beta, int max_blocks,
+                             hipStream_t s) {
+  lrn_bwd_v8_any<__bf16>((const __bf16*)x, (const __bf16*)y, (const __bf16*)dy,
+                         mask, g, (__bf16*)dx, db, relu != 0, rows, C, size,
+                         alpha, beta, max_blocks, s);
 }
 
 void ps_lrn_fwd_f32(const float* x, float* y, float* scale, int64_t rows,

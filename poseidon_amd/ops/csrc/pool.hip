@@ -9,6 +9,7 @@
 
 #include "ps_common.h"
 #include "ps_api.h"
+#include "ps_bwd_tail.h"
 
 namespace ps {
 
@@ -64,44 +65,65 @@ __global__ void maxpool_fwd_k(const T* x, T* y, uint8_t* mask, PoolGeom g) {
 }
 
 // gather: one thread per (n, h, w, V-chunk) scans covering windows
-template <typename T, int V>
-__global__ void maxpool_bwd_k(const T* dy, const uint8_t* mask, T* dx, PoolGeom g) {
+// RELU: x is the pool's bottom data, the post-ReLU output of the conv below
+// (conv -> relu -> pool): dx is masked by x > 0, replacing the in-place
+// relu_bwd that followed. BIAS: db[c] += column sum of the stored dx, the
+// conv's bias gradient; its launch keeps every thread on one channel chunk
+// (bias_flat_blocks) and passes g.C floats of dynamic LDS.
+template <typename T, int V, bool RELU, bool BIAS>
+__global__ void maxpool_bwd_k(const T* dy, const uint8_t* mask, const T* x,
+                              T* dx, float* db, PoolGeom g) {
   typedef T vec_t __attribute__((ext_vector_type(V)));
-  typedef uint8_t mvec_t __attribute__((ext_vector_type(V)));
+  extern __shared__ float part[];  // BIAS: g.C floats
   const int CV = g.C / V;
   int64_t total = (int64_t)g.N * g.H * g.W * CV;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total;
-       i += (int64_t)gridDim.x * blockDim.x) {
+  int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int c0 = (int)(i % CV) * V;  // BIAS: the same for every iteration
+  float bacc[V];
+#pragma unroll
+  for (int e = 0; e < V; ++e) bacc[e] = 0.f;
+  if (BIAS) bias_sum_init(part, g.C);
+  for (; i < total; i += (int64_t)gridDim.x * blockDim.x) {
     int cv = i % CV;
     int64_t t = i / CV;
     int w = t % g.W; t /= g.W;
     int h = t % g.H;
     int n = t / g.H;
-    int oh0 = (h + g.ph < g.kh) ? 0 : (h + g.ph - g.kh) / g.sh + 1;
-    int oh1 = min((h + g.ph) / g.sh + 1, g.Ho);
-    int ow0 = (w + g.pw < g.kw) ? 0 : (w + g.pw - g.kw) / g.sw + 1;
-    int ow1 = min((w + g.pw) / g.sw + 1, g.Wo);
     float acc[V];
-#pragma unroll
-    for (int e = 0; e < V; ++e) acc[e] = 0.f;
-    for (int oh = oh0; oh < oh1; ++oh)
-      for (int ow = ow0; ow < ow1; ++ow) {
-        int64_t oi = ((((int64_t)n * g.Ho + oh) * g.Wo + ow) * g.C) + cv * V;
-        int local = (h - (oh * g.sh - g.ph)) * g.kw + (w - (ow * g.sw - g.pw));
-        mvec_t mv = *reinterpret_cast<const mvec_t*>(&mask[oi]);
-        vec_t dv = *reinterpret_cast<const vec_t*>(&dy[oi]);
-#pragma unroll
-        for (int e = 0; e < V; ++e)
-          if ((int)mv[e] == local) acc[e] += to_f32(dv[e]);
-      }
+    maxpool_gather<T, V>(dy, mask, g, n, h, w, cv * V, acc);
     vec_t out;
+    if (RELU) {
+      vec_t xv = *reinterpret_cast<const vec_t*>(&x[i * V]);
+#pragma unroll
+      for (int e = 0; e < V; ++e) acc[e] = relu_mask(to_f32(xv[e]), acc[e]);
+    }
 #pragma unroll
     for (int e = 0; e < V; ++e) {
       T o;
       from_f32(acc[e], o);
       out[e] = o;
+      if (BIAS) bacc[e] += acc[e];
     }
     *reinterpret_cast<vec_t*>(&dx[i * V]) = out;
+  }
+  if (BIAS) bias_sum_flush<V>(part, bacc, c0, true, db, g.C);
+}
+
+// x null: no ReLU mask. db null: no bias sum (needs C % V == 0).
+template <typename T, int V>
+static void maxpool_bwd_tail(const T* dy, const uint8_t* mask, const T* x,
+                             T* dx, float* db, const PoolGeom& g,
+                             int max_blocks, hipStream_t s) {
+  const int CV = g.C / V;
+  const int64_t nvec = (int64_t)g.N * g.H * g.W * CV;
+  if (db) {
+    dim3 grid(bias_flat_blocks(nvec, CV, max_blocks));
+    if (x)
+      maxpool_bwd_k<T, V, true, true><<<grid, 256, g.C * 4, s>>>(dy, mask, x, dx, db, g);
+    else
+      maxpool_bwd_k<T, V, false, true><<<grid, 256, g.C * 4, s>>>(dy, mask, x, dx, db, g);
+  } else {
+    maxpool_bwd_k<T, V, true, false><<<ew_grid(nvec), 256, 0, s>>>(dy, mask, x, dx, db, g);
   }
 }
 
@@ -251,19 +273,36 @@ void ps_maxpool_bwd_f32(const float* dy, const uint8_t* mask, float* dx,
                         const PoolGeom* g, hipStream_t s) {
   int64_t rows = (int64_t)g->N * g->H * g->W;
   if (g->C % 4 == 0)
-    PS_POOL_LAUNCH(maxpool_bwd_k<float POOL_COMMA 4>, rows * (g->C / 4), dy, mask, dx, *g);
+    PS_POOL_LAUNCH(maxpool_bwd_k<float POOL_COMMA 4 POOL_COMMA false POOL_COMMA false>,
+                   rows * (g->C / 4), dy, mask, nullptr, dx, nullptr, *g);
   else
-    PS_POOL_LAUNCH(maxpool_bwd_k<float POOL_COMMA 1>, rows * g->C, dy, mask, dx, *g);
+    PS_POOL_LAUNCH(maxpool_bwd_k<float POOL_COMMA 1 POOL_COMMA false POOL_COMMA false>,
+                   rows * g->C, dy, mask, nullptr, dx, nullptr, *g);
+}
+// fused tail of conv -> relu -> max pool: x (may be null) masks dx by x > 0,
+// db (may be null) += colsum(dx). Needs C % 4 (f32) / C % 8 (bf16) == 0.
+void ps_maxpool_bwd_tail_f32(const float* dy, const uint8_t* mask,
+                             const float* x, float* dx, float* db,
+                             const PoolGeom* g, int max_blocks, hipStream_t s) {
+  maxpool_bwd_tail<float, 4>(dy, mask, x, dx, db, *g, max_blocks, s);
+}
+void ps_maxpool_bwd_tail_bf16(const void* dy, const uint8_t* mask,
+                              const void* x, void* dx, float* db,
+                              const PoolGeom* g, int max_blocks, hipStream_t s) {
+  maxpool_bwd_tail<__bf16, 8>((const __bf16*)dy, mask, (const __bf16*)x,
+                              (__bf16*)dx, db, *g, max_blocks, s);
 }
 void ps_maxpool_bwd_bf16(const void* dy, const uint8_t* mask, void* dx,
                          const PoolGeom* g, hipStream_t s) {
   int64_t rows = (int64_t)g->N * g->H * g->W;
   if (g->C % 8 == 0)
-    PS_POOL_LAUNCH(maxpool_bwd_k<__bf16 POOL_COMMA 8>, rows * (g->C / 8),
-                   (const __bf16*)dy, mask, (__bf16*)dx, *g);
+    PS_POOL_LAUNCH(maxpool_bwd_k<__bf16 POOL_COMMA 8 POOL_COMMA false POOL_COMMA false>,
+                   rows * (g->C / 8), (const __bf16*)dy, mask, nullptr,
+                   (__bf16*)dx, nullptr, *g);
   else
-    PS_POOL_LAUNCH(maxpool_bwd_k<__bf16 POOL_COMMA 1>, rows * g->C,
-                   (const __bf16*)dy, mask, (__bf16*)dx, *g);
+    PS_POOL_LAUNCH(maxpool_bwd_k<__bf16 POOL_COMMA 1 POOL_COMMA false POOL_COMMA false>,
+                   rows * g->C, (const __bf16*)dy, mask, nullptr, (__bf16*)dx,
+                   nullptr, *g);
 }
 void ps_avepool_fwd_f32(const float* x, float* y, const PoolGeom* g, hipStream_t s) {
   PS_POOL_LAUNCH(avepool_fwd_k<float>, (int64_t)g->N * g->Ho * g->Wo * g->C, x, y, *g);

@@ -58,6 +58,11 @@ void ps_dropout_bwd_f32(const float*, const uint8_t*, float*, int64_t, float,
 void ps_colsum_f32(const float*, float*, int64_t, int, hipStream_t);
 void ps_relu_fwd_bf16(const void*, void*, int64_t, float, hipStream_t);
 void ps_relu_bwd_bf16(const void*, const void*, void*, int64_t, float, hipStream_t);
+// slope-0 relu backward + bias colsum: (x, dy, dx, db, rows, C, max blocks)
+void ps_relu_bwd_bias_f32(const float*, const float*, float*, float*, int64_t,
+                          int, int, hipStream_t);
+void ps_relu_bwd_bias_bf16(const void*, const void*, void*, float*, int64_t,
+                           int, int, hipStream_t);
 void ps_sigmoid_fwd_bf16(const void*, void*, int64_t, hipStream_t);
 void ps_sigmoid_bwd_bf16(const void*, const void*, void*, int64_t, hipStream_t);
 void ps_tanh_fwd_bf16(const void*, void*, int64_t, hipStream_t);
@@ -97,6 +102,12 @@ void ps_stochpool_fwd_train_f32(const float*, float*, uint8_t*, const PoolGeom*,
 void ps_stochpool_fwd_test_f32(const float*, float*, const PoolGeom*, hipStream_t);
 void ps_maxpool_fwd_bf16(const void*, void*, uint8_t*, const PoolGeom*, hipStream_t);
 void ps_maxpool_bwd_bf16(const void*, const uint8_t*, void*, const PoolGeom*, hipStream_t);
+// fused conv -> relu -> max pool tail: (dy, mask, x | null, dx, db | null,
+// geom, max blocks)
+void ps_maxpool_bwd_tail_f32(const float*, const uint8_t*, const float*,
+                             float*, float*, const PoolGeom*, int, hipStream_t);
+void ps_maxpool_bwd_tail_bf16(const void*, const uint8_t*, const void*, void*,
+                              float*, const PoolGeom*, int, hipStream_t);
 void ps_avepool_fwd_bf16(const void*, void*, const PoolGeom*, hipStream_t);
 void ps_avepool_bwd_bf16(const void*, void*, const PoolGeom*, hipStream_t);
 
@@ -119,6 +130,17 @@ void ps_lrn_bwd_v8_f32(const float*, const float*, const float*, float*,
                        int64_t, int, int, float, float, hipStream_t);
 void ps_lrn_bwd_v8_bf16(const void*, const void*, const void*, void*, int64_t,
                         int, int, float, float, hipStream_t);
+// fused conv -> relu -> lrn [-> max pool] tail: (x, y, dy, pool mask | null,
+// pool geom | null, dx, db | null, relu, rows, C, size, alpha, beta, max
+// blocks of a launch that sums db). With a mask, dy is the POOL's top diff.
+void ps_lrn_bwd_v8_tail_f32(const float*, const float*, const float*,
+                            const uint8_t*, const PoolGeom*, float*, float*,
+                            int, int64_t, int, int, float, float, int,
+                            hipStream_t);
+void ps_lrn_bwd_v8_tail_bf16(const void*, const void*, const void*,
+                             const uint8_t*, const PoolGeom*, void*, float*,
+                             int, int64_t, int, int, float, float, int,
+                             hipStream_t);
 
 // softmax.hip
 void ps_softmax_rows_f32(const float*, float*, int64_t, int, hipStream_t);

@@ -372,6 +372,73 @@ def lrn_backward(x, y, scale, dy, size: int, alpha: float, beta: float):
 
 
 # ---------------------------------------------------------------------------
+# Fused backward tails of a conv block: conv -> relu -> [lrn] -> [max pool].
+# One kernel writes the conv's top diff (already masked by the in-place
+# ReLU) and adds its column sum into the conv's bias gradient. The CPU path
+# is the composition of the ops above.
+# ---------------------------------------------------------------------------
+
+def lrn_v8_ok(C: int, size: int) -> bool:
+    """Whether the GPU runs this LRN on its vec8 path (what the tails need)."""
+    return bool(_ext().lrn_v8_ok(int(C), int(size)))
+
+
+def set_bwd_tail_blocks(n: int) -> None:
+    """Block cap of the tail kernels that sum a bias gradient (0 = default);
+    tests lower it to make small tensors stride the grid."""
+    _ext().set_bwd_tail_blocks(int(n))
+
+
+def _bias_acc(dx, db) -> None:
+    if db is not None:
+        db += dx.sum(dim=(0, 2, 3)).to(db.dtype)
+
+
+def lrn_backward_tail(x, y, dy, size: int, alpha: float, beta: float,
+                      relu: bool = False, db=None, pool=None, dx_out=None):
+    """LRN backward with its neighbours folded in. pool = (mask, k, s, p) of
+    the MAX pool consuming this LRN's output: dy is then the POOL's top diff.
+    relu: x is a post-ReLU conv output, dx is masked by x > 0. db: f32 [C],
+    += the column sum of dx. GPU: the vec8 LRN path only (lrn_v8_ok)."""
+    if x.is_cuda:
+        mask, k, s, p = pool if pool is not None else (None, (0, 0), (0, 0),
+                                                       (0, 0))
+        return _ext().lrn_backward_tail(x, y, dy, size, alpha, beta, relu, db,
+                                        mask, k[0], k[1], s[0], s[1], p[0],
+                                        p[1], dx_out)
+    if pool is not None:
+        mask, k, s, p = pool
+        dy = pool_max_backward(dy, mask, x.shape, k, s, p)
+    _, scale = lrn_forward(x, size, alpha, beta)
+    dx = lrn_backward(x, y, scale, dy, size, alpha, beta)
+    if relu:
+        dx = relu_backward(x, dx, 0.0)
+    _bias_acc(dx, db)
+    return dx
+
+
+def pool_max_backward_tail(dy, mask, x, k, s, p, db=None, dx_out=None):
+    """MAX pool backward whose bottom x is a post-ReLU conv output: dx is
+    masked by x > 0 and its column sum is added into db (f32 [C])."""
+    if dy.is_cuda:
+        return _ext().pool_max_backward_tail(dy, mask, x, k[0], k[1], s[0],
+                                             s[1], p[0], p[1], db, dx_out)
+    dx = relu_backward(x, pool_max_backward(dy, mask, x.shape, k, s, p), 0.0)
+    _bias_acc(dx, db)
+    return dx
+
+
+def relu_backward_bias(x, dy, db):
+    """Slope-0 ReLU backward (in dy's buffer on the GPU) that also adds the
+    column sum of dx into db (f32 [C]): the relu -> conv tail."""
+    if x.is_cuda:
+        return _ext().relu_backward_bias(x, dy, db)
+    dx = relu_backward(x, dy, 0.0)
+    _bias_acc(dx, db)
+    return dx
+
+
+# ---------------------------------------------------------------------------
 # Softmax + losses
 # ---------------------------------------------------------------------------
 
