@@ -1302,6 +1302,9 @@ std::vector<Tensor> colsum_mt_prepare(std::vector<Tensor> dys,
                 d.size(1) % vec == 0 &&
                 dbs[t].scalar_type() == at::kFloat,
                 "colsum_mt: channels-last CUDA dy with C % 16B required");
+    // one kernel instantiation reads every dy of the table
+    TORCH_CHECK(d.scalar_type() == dys[0].scalar_type(),
+                "colsum_mt: all dys must share one dtype");
     int C = (int)d.size(1);
     int64_t R = d.numel() / C;
     // ~256K elements per block: coarse enough that terminal atomics on

@@ -193,6 +193,14 @@ class SGDSolver:
         dev = ctx().torch_device
         self._lr_dev = torch.zeros(1, dtype=torch.float32, device=dev)
         self._lr_dev.fill_(self.get_learning_rate())
+        # The warm-up passes below are full updates at the current rate that
+        # no iteration counts: keep what they change and put it back IN
+        # PLACE afterwards (the graph and the multi-tensor tables hold these
+        # tensors' addresses), so step(n) leaves the solver where eager
+        # step(n) does. Device-side per-iteration layer state (dropout's
+        # offset counter) still advances during the warm-up.
+        saved = [(t, t.clone()) for i in self.history
+                 for t in (self.net.params[i].blob.data, self.history[i])]
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):
@@ -206,6 +214,11 @@ class SGDSolver:
                 self._graph_body()
         torch.cuda.current_stream().wait_stream(side)
         torch.cuda.synchronize()
+        # before the capture, so a failed capture falls back to eager from
+        # the same state (recording the graph runs no kernel)
+        for t, t0 in saved:
+            t.copy_(t0)
+        del saved
         ok = True
         err: Optional[Exception] = None
         try:
