@@ -29,6 +29,7 @@
 
 #include "ps_common.h"
 #include "ps_api.h"
+#include "ps_gather.h"
 
 namespace ps {
 
@@ -70,31 +71,14 @@ template <> struct GemmTraits<__bf16> {
 // group slice (khw*Cg + cg). Returns the NHWC x address of k's element run
 // (contiguous along cg), or the zero page for padding. Valid for vector
 // loads that stay inside one cg-run (callers guarantee k%VEC==0, Cg%VEC==0).
-// exact unsigned divide by a small runtime constant via f32 reciprocal +
-// fixup (x < 2^24; integer division is ~40 cycles each and this decode runs
-// per staged vector)
-__device__ inline int fdiv_fix(int x, int d, float inv, int& rem) {
-  int q = (int)((float)x * inv);
-  rem = x - q * d;
-  if (rem < 0) { --q; rem += d; }
-  else if (rem >= d) { ++q; rem -= d; }
-  return q;
-}
-
+// The integer logic lives in ps_gather.h.
 template <typename T>
 __device__ inline const T* gather_addr(const GatherDesc& ga, int64_t row, int k) {
   if (k >= ga.kg_max) return (const T*)ga.zero;  // padded columns
-  int cg, kkw, ow, oh;
-  int khw = fdiv_fix(k, ga.Cg, ga.inv_Cg, cg);
-  int kkh = fdiv_fix(khw, ga.kw, ga.inv_kw, kkw);
-  int t = fdiv_fix((int)row, ga.Wo, ga.inv_Wo, ow);
-  int n = fdiv_fix(t, ga.Ho, ga.inv_Ho, oh);
-  int ih = oh * ga.sh - ga.ph + kkh;
-  int iw = ow * ga.sw - ga.pw + kkw;
-  if (ih < 0 || ih >= ga.H || iw < 0 || iw >= ga.W)
-    return (const T*)ga.zero;
-  return (const T*)ga.x + (((int64_t)n * ga.H + ih) * ga.W + iw) * ga.C
-         + ga.c0 + cg;
+  const GatherRow r = ps_gather_row(ga, (int)row);
+  const GatherTap t = ps_gather_tap(ga, k);
+  if (ps_gather_oob(ga, r, t, k)) return (const T*)ga.zero;
+  return (const T*)ga.x + ps_gather_offset(r, t);
 }
 
 // Direct global->LDS staging (glds): each wave-instruction moves 1 KiB
@@ -104,68 +88,112 @@ __device__ inline const T* gather_addr(const GatherDesc& ga, int64_t row, int k)
 // (the builtin writes wave-uniform-base + lane*16), so this path is used
 // for interior tiles of K-last operands only; fragment reads use the
 // unpadded BK stride.
-template <typename T, int ROWS, bool GATHER = false>
-__device__ inline void stage_glds(T* lds, const T* __restrict__ src,
-                                  int64_t lda, int row0, int k0, int wid,
-                                  int lane, const GatherDesc* ga = nullptr) {
+template <typename T, int ROWS>
+struct GldsMap {
   using TR = GemmTraits<T>;
-  constexpr int EPB = 16 / sizeof(T);            // elems per 16B lane-load
-  constexpr int LPR = TR::BK / EPB;              // lanes per row
-  constexpr int RPC = 64 / LPR;                  // rows per 1KB chunk
-  constexpr int CHUNKS = ROWS / RPC;
-  const int r_in = lane / LPR;
-  const int slot = lane % LPR;
-  // GATHER: the column decode (k -> kh,kw,cg) depends only on the lane's
-  // slot and the row-swizzle bit -- hoist both variants out of the chunk
-  // loop (the full per-chunk gather_addr decode measured 8.6 VALU per
-  // MFMA on the implicit conv forward)
-  int g_kkh[2], g_kkw[2], g_cg[2];
-  if (GATHER) {
-#pragma unroll
-    for (int p = 0; p < 2; ++p) {
-      const int kcp = (slot ^ (p << 1)) * EPB;
-      int khw = fdiv_fix(k0 + kcp, ga->Cg, ga->inv_Cg, g_cg[p]);
-      g_kkh[p] = fdiv_fix(khw, ga->kw, ga->inv_kw, g_kkw[p]);
-    }
+  static constexpr int EPB = 16 / (int)sizeof(T);  // elems per 16B lane-load
+  static constexpr int LPR = TR::BK / EPB;         // lanes per row
+  static constexpr int RPC = 64 / LPR;             // rows per 1KB chunk
+  static constexpr int CHUNKS = ROWS / RPC;
+  static constexpr int CPL = (CHUNKS + 3) / 4;     // chunks per lane
+  // Wave wid stages chunks wid, wid + 4, ...: all CPL of them when CHUNKS is
+  // a multiple of 4. Saying so at compile time matters: wid comes from
+  // threadIdx, so a run-time `ci < CHUNKS` is a per-lane compare and wraps
+  // every load after the first in exec-mask save/restore and a branch.
+  __device__ static inline bool live(int ci) {
+    return CHUNKS % 4 == 0 || ci < CHUNKS;
   }
-#pragma unroll
-  for (int ci = wid; ci < CHUNKS; ci += 4) {
-    const int row = ci * RPC + r_in;
-    // rule 21: the LDS image is XOR-swizzled by swizzling the SOURCE
-    // address per lane (glds writes lane-linear); reads apply the same XOR.
-    // ONE-bit (32 B-pair) swizzle, the 8-phase template's st_16x32 form:
-    // full-slot permutations also kill bank conflicts but destroy the
-    // request coalescer's lane-order contiguity (13x slower at L3-resident
-    // sizes); the pair swap keeps 32 B runs contiguous and still cuts
-    // ds_read_b128 conflicts 8-way -> 4-way. (A 2-bit slot swizzle keyed
-    // on row bits 1-2 makes the fragment reads fully conflict-free on
-    // paper, but flipping slot bit 0 reorders 16 B chunks within 32 B
-    // pairs on the WRITE side and measured -5%% end-to-end on AlexNet/VGG
-    // -- the global request coalescer penalty outweighs the LDS win.)
-    const int swb = (row >> 2) & 1;
-    const int kc = (slot ^ (swb << 1)) * EPB;
-    const T* g;
-    if (GATHER) {
-      int ow, oh;
-      const int t2 = fdiv_fix(row0 + row, ga->Wo, ga->inv_Wo, ow);
-      const int n2 = fdiv_fix(t2, ga->Ho, ga->inv_Ho, oh);
-      const int ih = oh * ga->sh - ga->ph + g_kkh[swb];
-      const int iw = ow * ga->sw - ga->pw + g_kkw[swb];
-      const bool oob = (k0 + kc >= ga->kg_max) || ih < 0 || ih >= ga->H ||
-                       iw < 0 || iw >= ga->W;
-      g = oob ? (const T*)ga->zero
-              : (const T*)ga->x +
-                    (((int64_t)n2 * ga->H + ih) * ga->W + iw) * ga->C +
-                    ga->c0 + g_cg[swb];
-    } else {
-      g = src + (int64_t)(row0 + row) * lda + k0 + kc;
-    }
+  // rule 21: the LDS image is XOR-swizzled by swizzling the SOURCE
+  // address per lane (glds writes lane-linear); reads apply the same XOR.
+  // ONE-bit (32 B-pair) swizzle, the 8-phase template's st_16x32 form:
+  // full-slot permutations also kill bank conflicts but destroy the
+  // request coalescer's lane-order contiguity (13x slower at L3-resident
+  // sizes); the pair swap keeps 32 B runs contiguous and still cuts
+  // ds_read_b128 conflicts 8-way -> 4-way. (A 2-bit slot swizzle keyed
+  // on row bits 1-2 makes the fragment reads fully conflict-free on
+  // paper, but flipping slot bit 0 reorders 16 B chunks within 32 B
+  // pairs on the WRITE side and measured -5%% end-to-end on AlexNet/VGG
+  // -- the global request coalescer penalty outweighs the LDS win.)
+  // The swizzle bit is row bit 2 and a chunk is a multiple of 8 rows, so a
+  // lane has ONE k column for all of its chunks.
+  static_assert(RPC % 8 == 0, "swizzle bit must not depend on the chunk");
+  __device__ static inline int r_in(int lane) { return lane / LPR; }
+  __device__ static inline int kc(int lane) {
+    const int swb = (r_in(lane) >> 2) & 1;
+    return ((lane % LPR) ^ (swb << 1)) * EPB;
+  }
+  __device__ static inline void load(T* lds, int ci, const void* g) {
     __builtin_amdgcn_global_load_lds(
         (const __attribute__((address_space(1))) void*)g,
         (__attribute__((address_space(3))) void*)(lds + ci * (1024 / (int)sizeof(T))),
         16, 0, 0);
   }
+};
+
+template <typename T, int ROWS>
+__device__ inline void stage_glds(T* lds, const T* __restrict__ src,
+                                  int64_t lda, int row0, int k0, int wid,
+                                  int lane) {
+  using MP = GldsMap<T, ROWS>;
+  const int r_in = MP::r_in(lane), kc = MP::kc(lane);
+#pragma unroll
+  for (int i = 0; i < MP::CPL; ++i) {
+    const int ci = wid + 4 * i;
+    if (!MP::live(ci)) break;
+    const int row = ci * MP::RPC + r_in;
+    MP::load(lds, ci, src + (int64_t)(row0 + row) * lda + k0 + kc);
+  }
 }
+
+// The same staging for a GATHERED A (implicit im2col): identical bytes into
+// identical LDS slots, the addresses walked instead of decoded. A lane
+// stages the same rows and the same column-within-the-tile for every k-tile,
+// so it decodes its rows (two divisions each) and its tap ONCE, keeps a byte
+// pointer to each row's window origin, and per tile pays two adds and two
+// unsigned compares for the padding test, one 64-bit add and one select per
+// chunk, plus one tap advance (ps_gather.h). The per-tile decode this
+// replaces was 181 VALU per tile against 51 for a plain A.
+template <typename T, int ROWS>
+struct GatherWalk {
+  using MP = GldsMap<T, ROWS>;
+  static constexpr int CPL = MP::CPL;
+  const char* rowp[CPL];  // x + row base, in bytes (see GatherRow::base)
+  int ih0[CPL], iw0[CPL];
+  GatherTap tap;
+  int k;  // the tap's column
+
+  __device__ inline void init(const GatherDesc& ga, int row0, int k0, int wid,
+                              int lane) {
+    const int r_in = MP::r_in(lane);
+#pragma unroll
+    for (int i = 0; i < CPL; ++i) {
+      const int ci = wid + 4 * i;
+      if (!MP::live(ci)) break;
+      const GatherRow r = ps_gather_row(ga, row0 + ci * MP::RPC + r_in);
+      rowp[i] = (const char*)ga.x + r.base * (int64_t)sizeof(T);
+      ih0[i] = r.ih0;
+      iw0[i] = r.iw0;
+    }
+    k = k0 + MP::kc(lane);
+    tap = ps_gather_tap(ga, k);
+  }
+
+  // stage the tile at the tap's column, then move the tap one tile on
+  __device__ inline void stage(T* lds, const GatherDesc& ga, int wid) {
+    const bool dead = k >= ga.kg_max;
+    const int64_t tapb = (int64_t)tap.off * (int64_t)sizeof(T);
+#pragma unroll
+    for (int i = 0; i < CPL; ++i) {
+      const int ci = wid + 4 * i;
+      if (!MP::live(ci)) break;
+      const bool oob = dead | ps_gather_pad(ga, ih0[i], iw0[i], tap);
+      const char* g = rowp[i] + tapb;
+      MP::load(lds, ci, oob ? (const char*)ga.zero : g);
+    }
+    ps_gather_tap_advance(ga, tap, k, GemmTraits<T>::BK);
+    k += GemmTraits<T>::BK;
+  }
+};
 
 // Guarded scalar staging of a PARTIAL final K-tile into the glds-layout
 // image (zero-filled beyond k_end): lets a GEMM whose K is not a BK
@@ -488,14 +516,24 @@ void gemm_kernel(const T* __restrict__ Abase, const T* __restrict__ Bbase,
       T* b_lin0 = b_lds[0];
       T* a_lin1 = a_lds[1];
       T* b_lin1 = b_lds[1];
-      stage_glds<T, BM, GA>(a_lin0, A, lda, m0, k_begin, wid, lane, &ga_a);
+      GatherWalk<T, BM> walk;  // GA only
+      if constexpr (GA) {
+        walk.init(ga_a, m0, k_begin, wid, lane);
+        walk.stage(a_lin0, ga_a, wid);
+      } else {
+        stage_glds<T, BM>(a_lin0, A, lda, m0, k_begin, wid, lane);
+      }
       stage_glds<T, BN>(b_lin0, B, ldb, n0, k_begin, wid, lane);
       __syncthreads();  // drains the in-flight glds (vmcnt 0) + barrier
       int cur2 = 0;
       for (int k0 = k_begin; k0 < k_end; k0 += BK) {
         if (k0 + BK < k_full) {
-          stage_glds<T, BM, GA>(cur2 ? a_lin0 : a_lin1, A, lda, m0, k0 + BK,
-                                wid, lane, &ga_a);
+          // consecutive full tiles: the walk's tap sits at k0 + BK
+          if constexpr (GA)
+            walk.stage(cur2 ? a_lin0 : a_lin1, ga_a, wid);
+          else
+            stage_glds<T, BM>(cur2 ? a_lin0 : a_lin1, A, lda, m0, k0 + BK,
+                              wid, lane);
           stage_glds<T, BN>(cur2 ? b_lin0 : b_lin1, B, ldb, n0, k0 + BK, wid,
                             lane);
         } else if (k0 + BK < k_end) {
@@ -702,8 +740,8 @@ __device__ inline void stage_kmaj_tr(__bf16* lds, const __bf16* src,
 #pragma unroll
     for (int p = 0; p < 4; ++p) {
       const int sl = slot ^ ((p << 1) & (LPR - 1));
-      int khw = fdiv_fix(c0 + sl * 8, ga->Cg, ga->inv_Cg, cg[p]);
-      kkh[p] = fdiv_fix(khw, ga->kw, ga->inv_kw, kkw[p]);
+      int khw = ps_fdiv_fix(c0 + sl * 8, ga->Cg, ga->inv_Cg, cg[p]);
+      kkh[p] = ps_fdiv_fix(khw, ga->kw, ga->inv_kw, kkw[p]);
     }
   }
 #pragma unroll
@@ -714,8 +752,8 @@ __device__ inline void stage_kmaj_tr(__bf16* lds, const __bf16* src,
     const __bf16* g2;
     if (GATHER) {
       int ow, oh;
-      const int t2 = fdiv_fix(k0 + row, ga->Wo, ga->inv_Wo, ow);
-      const int n2 = fdiv_fix(t2, ga->Ho, ga->inv_Ho, oh);
+      const int t2 = ps_fdiv_fix(k0 + row, ga->Wo, ga->inv_Wo, ow);
+      const int n2 = ps_fdiv_fix(t2, ga->Ho, ga->inv_Ho, oh);
       const int ih = oh * ga->sh - ga->ph + kkh[pi];
       const int iw = ow * ga->sw - ga->pw + kkw[pi];
       g2 = (ih < 0 || ih >= ga->H || iw < 0 || iw >= ga->W)
@@ -1144,7 +1182,15 @@ template <typename T, typename OUT, bool AK, bool BK_, bool HB,
           bool GA = false, bool GB = false>
 static void dispatch_tiles(const GemmLaunch& g, hipStream_t s) {
   int bm, bn;
-  pick_gemm_tile(g.M, g.N, &bm, &bn);
+  pick_gemm_tile(g.M, g.N, &bm, &bn, AK && BK_);
+  if constexpr (AK && BK_) {
+    // the N-fitting tiles, built for K-last x K-last only (conv forward and
+    // dgrad, FC forward)
+    if (bm == 128 && bn == 96)
+      return launch_tile<T, OUT, 128, 96, 2, 2, AK, BK_, HB, GA, GB>(g, s);
+    if (bm == 128 && bn == 48)
+      return launch_tile<T, OUT, 128, 48, 4, 1, AK, BK_, HB, GA, GB>(g, s);
+  }
   if (bm == 128 && bn == 32)
     launch_tile<T, OUT, 128, 32, 4, 1, AK, BK_, HB, GA, GB>(g, s);
   else if (bm == 32 && bn == 128)
@@ -1190,7 +1236,8 @@ extern "C" {
 // tr16 plan first (bf16 in, fp32 out only), else the generic plan
 void ps_gemm_plan(const GemmArgs* g, GemmPlan* plan) {
   const GemmShape sh = {g->M, g->N, g->K, g->batch, atomic_splitk_ok(*g),
-                        tn_tr_operands_ok(*g), g->gather_b != nullptr};
+                        tn_tr_operands_ok(*g), g->gather_b != nullptr,
+                        g->a_klast && g->b_klast};
   if (!ps_tn_tr_plan(sh, g_tr_tune, plan)) ps_generic_plan(sh, plan);
 }
 

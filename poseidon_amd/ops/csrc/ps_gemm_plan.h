@@ -28,6 +28,7 @@ struct GemmShape {
   bool atomic_ok;  // atomic split-K may add into C (atomic_splitk_ok)
   bool tr_ok;      // operands can take the tr16 TN kernel at all
   bool gather_b;   // B is gathered (implicit wgrad): no edge strips
+  bool nt;         // both operands K-last: the N-fitting tiles exist
 };
 
 // Manual override of the tr16 tile and split-K block target, 0 = planner's
@@ -96,19 +97,31 @@ PS_HD inline bool ps_tr_sub_live(int c0, int i, int cmax) {
 // (each A panel is re-staged once per N-tile and vice versa). ALPHA ~= MACs
 // the matrix cores retire per element the memory system delivers (bf16:
 // ~1.25e15 MAC/s vs ~3.2e12 elem/s -> ~400).
-inline void pick_gemm_tile(int M, int N, int* bm_out, int* bn_out) {
-  const int cand[6][2] = {{128, 128}, {128, 32}, {32, 128}, {64, 64},
-                          {128, 16},  {16, 128}};
+// `narrow` (both operands K-last, the only layout they are built for) adds
+// the N-fitting tiles 128x96 (2x2 waves of 64x48) and 128x48 (4x1 waves of
+// 32x48). They are taken only where they cut the padded N of the best
+// square-menu tile -- N = 48 / 96 / 192 and their neighbours, where a 128- or
+// 64-column tile idles a quarter of its MFMAs -- not wherever the staging
+// term alone would prefer them (N = 64 stays on 64x64).
+inline void pick_gemm_tile(int M, int N, int* bm_out, int* bn_out,
+                           bool narrow = false) {
+  const int cand[8][2] = {{128, 128}, {128, 32}, {32, 128}, {64, 64},
+                          {128, 16},  {16, 128}, {128, 96}, {128, 48}};
   const double ALPHA = 400.0;
-  double best = 0;
-  for (int i = 0; i < 6; ++i) {
+  double best = -1.0;
+  int64_t best_npad = 0;
+  *bm_out = cand[0][0];
+  *bn_out = cand[0][1];
+  for (int i = 0; i < (narrow ? 8 : 6); ++i) {
     int bm = cand[i][0], bn = cand[i][1];
     int64_t tm = (M + bm - 1) / bm, tn = (N + bn - 1) / bn;
     double flops = (double)(tm * bm) * (tn * bn) / ALPHA;  // (x K, common)
     double staging = (double)tm * bm * tn + (double)tn * bn * tm;
     double cost = flops + staging;
-    if (i == 0 || cost < best) {
+    if (i >= 6 && tn * bn >= best_npad) continue;
+    if (best < 0 || cost < best) {
       best = cost;
+      best_npad = tn * bn;
       *bm_out = bm;
       *bn_out = bn;
     }
@@ -253,7 +266,7 @@ inline int ps_tr_grid_z(const GemmPlan& p) {
 inline void ps_generic_plan(const GemmShape& g, GemmPlan* p) {
   *p = {false, 1, 0, 0, 0, 0, 0, 0};
   int tbm, tbn;
-  pick_gemm_tile(g.M, g.N, &tbm, &tbn);
+  pick_gemm_tile(g.M, g.N, &tbm, &tbn, g.nt);
   const int64_t tiles =
       (int64_t)((g.M + tbm - 1) / tbm) * ((g.N + tbn - 1) / tbn);
   if (g.atomic_ok && tiles < 384 && g.K >= 512) {
