@@ -27,6 +27,12 @@ class _Context:
     use_sfb: bool = True                # sufficient-factor broadcast for IP layers
     sfb_min_elems: int = 1 << 20        # only factor-broadcast large FC grads
     distributed: bool = False
+    # DATA / IMAGE_DATA layers ship raw uint8 records and run the
+    # DataTransformer arithmetic on the device (ops.data_transform); off by
+    # default, PS_DEVICE_TRANSFORM=1 turns it on at import
+    device_transform: bool = field(
+        default_factory=lambda: os.environ.get("PS_DEVICE_TRANSFORM", "0")
+        not in ("", "0"))
     phase_stack: list = field(default_factory=list)
 
     @property
@@ -48,7 +54,8 @@ def ctx() -> _Context:
 
 def init(device: Optional[str] = None, rank: Optional[int] = None,
          world_size: Optional[int] = None, seed: Optional[int] = None,
-         compute_dtype: Optional[torch.dtype] = None) -> _Context:
+         compute_dtype: Optional[torch.dtype] = None,
+         device_transform: Optional[bool] = None) -> _Context:
     """(Re)configure the global context. Reads torchrun env vars when args
     are omitted."""
     if rank is None:
@@ -72,4 +79,6 @@ def init(device: Optional[str] = None, rank: Optional[int] = None,
         torch.manual_seed(seed + 1000 * rank)
     if compute_dtype is not None:
         _ctx.compute_dtype = compute_dtype
+    if device_transform is not None:
+        _ctx.device_transform = bool(device_transform)
     return _ctx

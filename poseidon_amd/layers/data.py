@@ -123,6 +123,17 @@ class _PrefetchingDataLayer(Layer):
 
     exact_num_bottom = 0
 
+    # Device-transform path (ctx().device_transform, DATA / IMAGE_DATA over
+    # uint8 records): the thread ships RAW records plus the transformer's
+    # draws, stage() copies them to the device and forward() runs
+    # ops.data_transform into a persistent top. With external_staging set
+    # (by a solver that replays forward() from a hipGraph) forward() leaves
+    # the stage() call to its caller; staged_ahead tells the next forward()
+    # that its batch is staged already (a solver handing staging back).
+    on_device = False
+    external_staging = False
+    staged_ahead = False
+
     def _start_prefetch(self) -> None:
         self._ready = threading.Event()
         self._taken = threading.Event()
@@ -136,7 +147,10 @@ class _PrefetchingDataLayer(Layer):
         while not self._stop:
             self._taken.wait()
             self._taken.clear()
-            self._batch = self._load_batch()
+            try:
+                self._batch = self._load_batch()
+            except Exception as e:  # noqa: BLE001 -- re-raised by the taker
+                self._batch = e
             self._ready.set()
 
     def _next_batch(self):
@@ -144,10 +158,112 @@ class _PrefetchingDataLayer(Layer):
         self._ready.clear()
         batch = self._batch
         self._taken.set()
+        if isinstance(batch, Exception):
+            raise batch
         return batch
 
     def _load_batch(self):
         raise NotImplementedError
+
+    # -- device-transform path ------------------------------------------
+    def _setup_device_path(self, c: int, h: int, w: int) -> None:
+        """The records are c x h x w uint8. Two rotating host sets (pinned
+        on a GPU context), each [raw bytes | pad to 16 | int32 params] in
+        one buffer plus fp32 labels, and one device staging buffer of the
+        same layout: a batch crosses in two copies."""
+        cx = ctx()
+        dev = cx.torch_device
+        cuda = dev.type == "cuda"
+        self.on_device = True
+        self.raw_shape = (c, h, w)
+        # the draw the host path's sample transform makes at setup, so both
+        # paths see the same draws from the first batch on
+        self.transform.draw(h, w)
+        mode, mean, scale, crop = self.transform.device_spec(c, h, w)
+        self.shape = (c, crop, crop) if crop else (c, h, w)
+        self._mean_mode, self._scale = mode, scale
+        self._mean_dev = mean.to(dev) if mean is not None else None
+        n = self.batch
+        nraw = n * c * h * w
+        poff = (nraw + 15) // 16 * 16
+
+        def split(buf):
+            return (buf[:nraw].view(n, c, h, w),
+                    buf[poff:poff + 12 * n].view(torch.int32).view(n, 3))
+
+        self._host_sets = []
+        for _ in range(2):
+            buf = torch.zeros(poff + 12 * n, dtype=torch.uint8,
+                              pin_memory=cuda)
+            labels = torch.zeros(n, dtype=torch.float32, pin_memory=cuda)
+            raw, params = split(buf)
+            self._host_sets.append({
+                "buf": buf, "labels": labels, "raw": raw.numpy(),
+                "params": params.numpy(), "labels_np": labels.numpy(),
+                # recorded once the set's H2D copies are enqueued
+                "event": torch.cuda.Event() if cuda else None,
+                "recorded": False})
+        self._fill = 0
+        self._stage_dev = torch.zeros(poff + 12 * n, dtype=torch.uint8,
+                                      device=dev)
+        self._raw_dev, self._params_dev = split(self._stage_dev)
+        self._data_out: Optional[torch.Tensor] = None
+        self._label_out: Optional[torch.Tensor] = None
+
+    def _raw_record(self, i: int):
+        """(uint8 [c,h,w] array, label) of the batch's i-th record; advances
+        the cursor."""
+        raise NotImplementedError
+
+    def _load_raw_batch(self):
+        hs = self._host_sets[self._fill]
+        self._fill ^= 1
+        if hs["recorded"]:
+            hs["event"].synchronize()  # its last copies have left the set
+        _, h, w = self.raw_shape
+        for i in range(self.batch):
+            rec, label = self._raw_record(i)
+            if rec.dtype != np.uint8 or rec.shape != self.raw_shape:
+                raise ValueError(
+                    f"layer {self.name!r}: record of {rec.dtype} "
+                    f"{rec.shape} on the device-transform path, which was "
+                    f"set up for uint8 {self.raw_shape}")
+            hs["raw"][i] = rec
+            hs["params"][i] = self.transform.draw(h, w)
+            hs["labels_np"][i] = label
+        return hs
+
+    def _reshape_device(self, top) -> None:
+        if self._data_out is None:
+            cx = ctx()
+            self._data_out = torch.zeros((self.batch,) + self.shape,
+                                         dtype=cx.compute_dtype,
+                                         device=cx.torch_device)
+            self._label_out = torch.zeros(self.batch, dtype=torch.float32,
+                                          device=cx.torch_device)
+        top[0].data = self._data_out  # the same tensors every time
+        if len(top) > 1:
+            top[1].data = self._label_out
+
+    def stage(self) -> None:
+        """Take the next prefetched batch and enqueue its copies to the
+        device on the current stream: raw records + params into the staging
+        buffer, labels straight into the label top."""
+        hs = self._next_batch()
+        self._stage_dev.copy_(hs["buf"], non_blocking=True)
+        self._label_out.copy_(hs["labels"], non_blocking=True)
+        if hs["event"] is not None:
+            hs["event"].record()
+            hs["recorded"] = True
+
+    def _forward_device(self, top) -> None:
+        from ..ops import functional as ops
+        if self.staged_ahead:
+            self.staged_ahead = False
+        elif not self.external_staging:
+            self.stage()
+        ops.data_transform(self._raw_dev, self._params_dev, self._mean_dev,
+                           self._mean_mode, self._scale, self._data_out)
 
     def backward(self, top, propagate_down, bottom) -> None:
         pass
@@ -191,12 +307,32 @@ class DataLayer(_PrefetchingDataLayer):
         rng = np.random.default_rng(c.seed + 131 * c.rank)
         self.transform = DataTransformer(self.param.transform_param,
                                          self.phase, rng)
-        first = datum_to_array(self.db.get(0))
-        sample = self.transform(first)
-        self.shape = sample.shape
+        d0 = self.db.get(0)
+        first = datum_to_array(d0)
+        if c.device_transform and d0.has("data") and len(d0.data):
+            self._setup_device_path(*first.shape)
+        else:  # host path; float_data records always take it
+            sample = self.transform(first)
+            self.shape = sample.shape
         self._start_prefetch()
 
+    def _raw_record(self, i: int):
+        d = self.db.get(self.cursor % len(self.db))
+        self.cursor += self.stride
+        if not (d.has("data") and len(d.data)):
+            raise ValueError(
+                f"layer {self.name!r}: float_data record on the "
+                "device-transform path, which ships uint8 records only")
+        dims = (d.channels, d.height, d.width)
+        if len(d.data) != dims[0] * dims[1] * dims[2]:
+            raise ValueError(f"layer {self.name!r}: Datum of {dims} carries "
+                             f"{len(d.data)} bytes")
+        return (np.frombuffer(d.data, dtype=np.uint8).reshape(dims),
+                d.label or 0)
+
     def _load_batch(self):
+        if self.on_device:
+            return self._load_raw_batch()
         data = np.empty((self.batch,) + self.shape, dtype=np.float32)
         labels = np.empty((self.batch,), dtype=np.float32)
         for i in range(self.batch):
@@ -207,11 +343,15 @@ class DataLayer(_PrefetchingDataLayer):
         return data, labels
 
     def reshape(self, bottom, top) -> None:
+        if self.on_device:
+            return self._reshape_device(top)
         top[0].reshape((self.batch,) + self.shape)
         if len(top) > 1:
             top[1].reshape(self.batch)
 
     def forward(self, bottom, top) -> None:
+        if self.on_device:
+            return self._forward_device(top)
         data, labels = self._next_batch()
         c = ctx()
         top[0].data = torch.from_numpy(data).to(c.torch_device, c.compute_dtype,
@@ -247,8 +387,13 @@ class ImageDataLayer(_PrefetchingDataLayer):
         rng = np.random.default_rng(c.seed + 977 * c.rank)
         self.transform = DataTransformer(self.param.transform_param,
                                          self.phase, rng)
-        sample = self.transform(self._read(self.entries[0][0]))
-        self.shape = sample.shape
+        if c.device_transform:
+            # decoded RGB images are uint8: kept as such, nothing is lost
+            self.on_device = True
+            self._setup_device_path(*self._read(self.entries[0][0]).shape)
+        else:
+            sample = self.transform(self._read(self.entries[0][0]))
+            self.shape = sample.shape
         self._start_prefetch()
 
     def _read(self, path: str) -> np.ndarray:
@@ -256,11 +401,19 @@ class ImageDataLayer(_PrefetchingDataLayer):
         img = Image.open(path).convert("RGB")
         if self.new_h and self.new_w:
             img = img.resize((self.new_w, self.new_h))
-        arr = np.asarray(img, dtype=np.float32)  # HWC RGB
+        # HWC RGB
+        arr = np.asarray(img, dtype=np.uint8 if self.on_device else np.float32)
         # Caffe stores BGR; match channel order for mean-file compat
         return np.ascontiguousarray(arr[:, :, ::-1].transpose(2, 0, 1))
 
+    def _raw_record(self, i: int):
+        path, lbl = self.entries[self.cursor % len(self.entries)]
+        self.cursor += 1
+        return self._read(path), lbl
+
     def _load_batch(self):
+        if self.on_device:
+            return self._load_raw_batch()
         data = np.empty((self.batch,) + self.shape, dtype=np.float32)
         labels = np.empty((self.batch,), dtype=np.float32)
         for i in range(self.batch):
@@ -271,10 +424,14 @@ class ImageDataLayer(_PrefetchingDataLayer):
         return data, labels
 
     def reshape(self, bottom, top) -> None:
+        if self.on_device:
+            return self._reshape_device(top)
         top[0].reshape((self.batch,) + self.shape)
         top[1].reshape(self.batch)
 
     def forward(self, bottom, top) -> None:
+        if self.on_device:
+            return self._forward_device(top)
         data, labels = self._next_batch()
         c = ctx()
         top[0].data = torch.from_numpy(data).to(c.torch_device, c.compute_dtype,

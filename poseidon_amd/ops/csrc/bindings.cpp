@@ -1415,9 +1415,65 @@ void colsum_acc(const Tensor& dy, Tensor db) {
   PS_CALL(colsum, is_bf16(d), P(d), db.data_ptr<float>(), R, C, stream());
 }
 
+// ---------------------------------------------------------------------------
+// data-layer transform: raw uint8 records -> the layer's NCHW top, in place
+// ---------------------------------------------------------------------------
+
+void data_transform(const Tensor& raw, const Tensor& params,
+                    const c10::optional<Tensor>& mean, int64_t mean_mode,
+                    double scale, Tensor out) {
+  TORCH_CHECK(raw.is_cuda() && params.is_cuda() && out.is_cuda(),
+              "data_transform: expected device tensors");
+  TORCH_CHECK(raw.scalar_type() == at::kByte && raw.dim() == 4 &&
+                  raw.is_contiguous(),
+              "data_transform: raw must be contiguous uint8 [N,C,H,W]");
+  const int64_t N = raw.size(0), C = raw.size(1), H = raw.size(2),
+                W = raw.size(3);
+  TORCH_CHECK(params.scalar_type() == at::kInt && params.is_contiguous() &&
+                  params.dim() == 2 && params.size(0) == N &&
+                  params.size(1) == 3,
+              "data_transform: params must be contiguous int32 [N,3]");
+  check_float_like(out, "data_transform out");
+  TORCH_CHECK(out.dim() == 4 && out.is_contiguous() && out.size(0) == N &&
+                  out.size(1) == C && out.size(2) >= 1 && out.size(2) <= H &&
+                  out.size(3) >= 1 && out.size(3) <= W,
+              "data_transform: out must be contiguous [N,C,Ho,Wo] with "
+              "Ho <= H, Wo <= W");
+  TORCH_CHECK(C * H * W < (int64_t(1) << 31) && N < (int64_t(1) << 29),
+              "data_transform: record too large");
+  TORCH_CHECK((uintptr_t)out.data_ptr() %
+                      (PS_TRANSFORM_VEC * out.element_size()) == 0,
+              "data_transform: out must be aligned to 8 elements");
+  int64_t want = 0;
+  switch (mean_mode) {
+    case PS_MEAN_NONE: break;
+    case PS_MEAN_SCALAR: want = 1; break;
+    case PS_MEAN_CHANNEL: want = C; break;
+    case PS_MEAN_IMAGE: want = C * H * W; break;
+    default: TORCH_CHECK(false, "data_transform: bad mean_mode ", mean_mode);
+  }
+  const float* mp = nullptr;
+  if (want) {
+    TORCH_CHECK(mean.has_value() && mean->is_cuda() &&
+                    mean->scalar_type() == at::kFloat &&
+                    mean->is_contiguous() && mean->numel() == want,
+                "data_transform: mean must be contiguous fp32 with ", want,
+                " elements");
+    mp = mean->data_ptr<float>();
+  }
+  TransformGeom g;
+  g.N = (int)N; g.C = (int)C; g.H = (int)H; g.W = (int)W;
+  g.Ho = (int)out.size(2); g.Wo = (int)out.size(3);
+  g.mean_mode = (int)mean_mode;
+  g.scale = (float)scale;
+  PS_CALL(data_transform, is_bf16(out), raw.data_ptr<uint8_t>(),
+          params.data_ptr<int>(), mp, P(out), &g, stream());
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
+  m.def("data_transform", &data_transform);
   m.def("gemm", &gemm);
   m.def("linear_forward", &linear_forward);
   m.def("linear_backward", &linear_backward);

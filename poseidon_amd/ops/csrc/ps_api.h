@@ -5,6 +5,7 @@
 
 #include "ps_conv_plan.h"  // ConvGeom, GatherDesc, ConvPlan
 #include "ps_gemm_plan.h"  // GemmPlan, TrTune
+#include "ps_transform.h"  // TransformGeom, PS_MEAN_*
 
 struct GemmArgs {
   const void* A;
@@ -179,6 +180,13 @@ void ps_repack_mt(const void* descs, const void* chunks, int nchunks,
                   hipStream_t);
 void ps_unpack_mt(const void* descs, const void* chunks, int nchunks,
                   hipStream_t);
+
+// transform.hip: (raw uint8 [N,C,H,W], params int32 [N,3], mean | null, out
+// [N,C,Ho,Wo], geom). out must be aligned to 8 of its elements.
+void ps_data_transform_f32(const uint8_t*, const int*, const float*, float*,
+                           const TransformGeom*, hipStream_t);
+void ps_data_transform_bf16(const uint8_t*, const int*, const float*, void*,
+                            const TransformGeom*, hipStream_t);
 
 // im2col.hip
 void ps_chan_concat4_f32(float*, void* const*, const int*, int, int, int64_t,

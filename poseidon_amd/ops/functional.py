@@ -749,6 +749,47 @@ def split_channels(x, sizes, outs_cache=None, relu_masks=None):
 
 
 # ---------------------------------------------------------------------------
+# Data-layer transform (mean, crop, mirror, scale, cast) of raw uint8 records
+# ---------------------------------------------------------------------------
+
+MEAN_NONE, MEAN_SCALAR, MEAN_CHANNEL, MEAN_IMAGE = 0, 1, 2, 3
+
+
+def data_transform(raw: torch.Tensor, params: torch.Tensor,
+                   mean: Optional[torch.Tensor], mean_mode: int, scale: float,
+                   out: torch.Tensor) -> None:
+    """out[n,c,h,w] = (float(raw[n,c,h+h_off,ws]) - mean[c,h+h_off,ws]) * scale
+    with (h_off, w_off, flip) = params[n] and ws = w_off + w, or
+    w_off + Wo-1-w when flip: DataTransformer's arithmetic (one fp32
+    subtract, one fp32 multiply, one rounding to out's dtype), written INTO
+    out [N,C,Ho,Wo]. raw is uint8 [N,C,H,W], params int32 [N,3], mean fp32
+    with 1 / C / C*H*W elements per mean_mode (MEAN_*)."""
+    if raw.is_cuda:
+        _ext().data_transform(raw, params, mean, int(mean_mode), float(scale),
+                              out)
+        return
+    N, C, H, W = raw.shape
+    Ho, Wo = int(out.shape[2]), int(out.shape[3])
+    assert tuple(out.shape) == (N, C, Ho, Wo) and Ho <= H and Wo <= W
+    x = raw.to(torch.float32)
+    if mean_mode == MEAN_IMAGE:
+        x = x - mean.reshape(1, C, H, W)
+    elif mean_mode == MEAN_CHANNEL:
+        x = x - mean.reshape(1, C, 1, 1)
+    elif mean_mode == MEAN_SCALAR:
+        x = x - mean.reshape(())
+    p = params.long()
+    h_off = p[:, 0:1].clamp(0, H - Ho)
+    w_off = p[:, 1:2].clamp(0, W - Wo)
+    w = torch.arange(Wo)
+    hi = h_off + torch.arange(Ho)                                  # [N,Ho]
+    wi = w_off + torch.where(p[:, 2:3] != 0, Wo - 1 - w, w)        # [N,Wo]
+    g = x[torch.arange(N).view(N, 1, 1, 1), torch.arange(C).view(1, C, 1, 1),
+          hi.view(N, 1, Ho, 1), wi.view(N, 1, 1, Wo)]
+    out.copy_(g * torch.tensor(float(scale), dtype=torch.float32))
+
+
+# ---------------------------------------------------------------------------
 # Metrics
 # ---------------------------------------------------------------------------
 

@@ -108,6 +108,11 @@ class SGDSolver:
         self._graph = None
         self._graph_loss = None
         self._lr_dev: Optional[torch.Tensor] = None
+        # data layers on the device-transform path whose stage() the graphed
+        # loop calls before each replay, and whether the batch now in their
+        # staging buffers has not been trained on yet
+        self._staged_layers: list = []
+        self._batch_staged = False
         # multi-tensor update table (one kernel for ALL params); keyed on
         # tensor identities so restore()/load_weights() invalidate it
         self._mt = None
@@ -133,16 +138,39 @@ class SGDSolver:
             import torch.distributed as dist
             if dist.get_backend() != "nccl":
                 return False  # gloo collectives are host-side: not capturable
+        staged = []
         for layer in self.net.layers:
             t = layer.type_name
             if t in ("DATA", "IMAGE_DATA", "MEMORY_DATA", "WINDOW_DATA"):
-                return False  # per-iter host work cannot replay
+                if not getattr(layer, "on_device", False):
+                    return False  # per-iter host work cannot replay
+                # device-transform path: its only host work is stage(), which
+                # _step_graphed calls before each replay
+                staged.append(layer)
             if t == "DUMMY_DATA" and any(layer.refill):
                 layer.forward(self.net.bottoms[self.net.layers.index(layer)],
                               self.net.tops[self.net.layers.index(layer)])
                 layer.refill = [False] * len(layer.refill)  # freeze fills
+        for layer in staged:
+            layer.external_staging = True
+        self._staged_layers = staged
+        self._batch_staged = False
         self._use_graph = True
         return True
+
+    def _stage_inputs(self) -> None:
+        for layer in self._staged_layers:
+            layer.stage()
+
+    def _release_staging(self) -> None:
+        """Back to eager: the layers' forward() stages again. A batch that
+        is staged but not trained on yet is the one the next forward()
+        uses."""
+        for layer in self._staged_layers:
+            layer.external_staging = False
+            layer.staged_ahead = self._batch_staged
+        self._staged_layers = []
+        self._batch_staged = False
 
     def _graph_body(self) -> torch.Tensor:
         loss = self.forward_backward()
@@ -201,6 +229,12 @@ class SGDSolver:
         # offset counter) still advances during the warm-up.
         saved = [(t, t.clone()) for i in self.history
                  for t in (self.net.params[i].blob.data, self.history[i])]
+        # staged data layers: the warm-up and the capture all run on the
+        # first batch and consume no further records; the first replay
+        # trains on it
+        if self._staged_layers and not self._batch_staged:
+            self._stage_inputs()
+            self._batch_staged = True
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):
@@ -247,6 +281,16 @@ class SGDSolver:
         if self._graph is None:
             self._capture_graph()
         while iters > 0:
+            # same boundaries as the eager loop, outside the graph
+            if (p.snapshot and self.iter > 0
+                    and self.iter % p.snapshot == 0):
+                self.snapshot()
+            if (p.test_interval and self.iter % p.test_interval == 0
+                    and (self.iter > 0 or bool(p.test_initialization))):
+                self.test_all()
+            if self._staged_layers and not self._batch_staged:
+                self._stage_inputs()
+            self._batch_staged = False
             self._lr_dev.fill_(self.get_learning_rate())
             self._graph.replay()
             if p.display and self.iter % p.display == 0:
@@ -342,6 +386,7 @@ class SGDSolver:
                       "falling back to eager", file=sys.stderr, flush=True)
                 self._use_graph = False
                 self._graph = None
+                self._release_staging()
         last_loss = 0.0
         p = self.param
         while iters > 0:

@@ -37,6 +37,15 @@ def main(argv=None):
                     help="dump per-layer fwd/bwd timing YAML here (the "
                          "Bösen caffe_stats.yaml analogue)")
     ap.add_argument("--cpu", action="store_true", help="force CPU mode")
+    ap.add_argument("--device-transform", action="store_true",
+                    help="DATA / IMAGE_DATA layers ship raw uint8 records and "
+                         "run mean/crop/mirror/scale on the device (default "
+                         "off; PS_DEVICE_TRANSFORM=1 does the same)")
+    ap.add_argument("--graph", action="store_true",
+                    help="replay the training iteration from a hipGraph "
+                         "(DB-backed data layers need --device-transform); "
+                         "falls back to eager where the net cannot be "
+                         "captured")
     args = ap.parse_args(argv)
 
     import poseidon_amd as pa
@@ -50,11 +59,18 @@ def main(argv=None):
     seed = int(solver_param.random_seed)
     pa.init(device="cuda" if use_gpu else "cpu",
             seed=seed if seed >= 0 else 1,
-            compute_dtype=cd)
+            compute_dtype=cd,
+            device_transform=True if args.device_transform else None)
 
     solver = get_solver(solver_param, use_sfb=args.svb)
     if args.weights:
         solver.load_weights(args.weights)
+    if args.graph:
+        took = solver.enable_graph()
+        if pa.ctx().is_root():
+            print(f"[poseidon] hipgraph requested: "
+                  f"{'enabled' if took else 'not capturable, running eager'}",
+                  flush=True)
     stats = None
     if args.stats:
         from poseidon_amd.utils.stats import LayerStats
@@ -62,6 +78,10 @@ def main(argv=None):
         ctx_mgr = stats.timed()
         ctx_mgr.__enter__()
     solver.solve(resume_file=args.snapshot or None)
+    if args.graph and pa.ctx().is_root():
+        # what actually ran: a failed capture falls back to eager
+        graphed = bool(solver._use_graph and solver._graph is not None)
+        print(f"[poseidon] hipgraph: {str(graphed).lower()}", flush=True)
     if stats is not None:
         ctx_mgr.__exit__(None, None, None)
         if pa.ctx().is_root():
