@@ -164,8 +164,6 @@ void run_gemm(const Tensor& A, const Tensor& B, Tensor& C,
   g.bias = bias;
   g.M = M; g.N = N; g.K = K;
   g.lda = lda; g.ldb = ldb; g.ldc = ldc;
-  g.strideA = 0; g.strideB = 0; g.strideC = 0;
-  g.batch = 1;
   g.alpha = alpha; g.beta = beta;
   g.a_klast = a_klast; g.b_klast = b_klast;
   g.gather_a = gather_a;

@@ -7,17 +7,34 @@
 //     ([K][lda], lda>=M; staged with an on-the-fly transpose into LDS)
 //   - op(B) is [K,N]: stored as [N][ldb] K-last (the natural NT form) or
 //     [K][ldb] K-major (staged transposed)
-//   - batched via grid.z with element strides (stride 0 broadcasts weights)
+//   - A (K-last) or B (K-major) may be GATHERED from an NHWC activation
+//     instead of read from a matrix (implicit im2col, ps_gather.h)
 //
-// Structure (per /opt/skills/guides/cdna_hip_programming.md §5): 128x128
-// block tile, 256 threads = 4 waves in a 2x2 arrangement, each wave owns a
-// 64x64 sub-tile as 4x4 fragments of v_mfma_f32_16x16x32_bf16 (bf16, K
-// step 32) or v_mfma_f32_16x16x4_f32 (fp32, K step 4, exact f32 at the
-// 155 TF vector-rate ceiling). LDS tiles are K-contiguous with padded rows
-// (+16 B) to keep ds_read_b128 lane groups off a single bank.
+// Every launch decision -- path, tile, split-K, K slice, XCD placement -- is
+// made once by ps_gemm_plan (policy in ps_gemm_plan.h, checked on the host by
+// tests/gemm_plan_host.cpp); ps_gemm_run executes that plan. Two kernels:
 //
-// This is the correctness-first register-staged variant; the glds
-// (global_load_lds) pipelined variant is the planned fast path.
+// gemm_kernel, the generic tiles (PS_GEMM_TILE_LIST): every forward, every
+//   dgrad, every fp32 GEMM and whatever tr16 does not take. 256 threads = 4
+//   waves, each owning a sub-tile of 16x16 fragments of
+//   v_mfma_f32_16x16x32_bf16 (bf16, K step 32) or v_mfma_f32_16x16x4_f32
+//   (fp32, K step 4, exact f32 at the 155 TF vector-rate ceiling); LDS is
+//   double-buffered. A block picks one of two main loops:
+//   - glds: interior tiles of K-last x K-last operands with 16 B-aligned
+//     rows stage by global_load_lds, 16 B per lane straight into a linear,
+//     source-swizzled LDS image; a gathered A walks its addresses
+//     (GatherWalk); a K % BK tail is staged by guarded scalar writes.
+//   - register-staged: everything else (edge tiles, K-major operands,
+//     unaligned rows). Guarded vector loads into registers, written to LDS
+//     rows padded by 16 B (K-last) or block-transposed and XOR-swizzled
+//     (K-major), one tile ahead of the MFMAs.
+//   Split-K slices either store raw partials to a workspace that
+//   splitk_reduce_k combines, or add atomically into a zeroed f32 C.
+//
+// gemm_tn_tr_kernel, the tr16 tiles (PS_TR_TILE_LIST): bf16 in / f32 out with
+//   both operands K-major -- the weight gradients. Natural [k][col] images
+//   staged by glds and read through ds_read_b64_tr_b16. Covers the 16 x 64
+//   aligned interior; edge strips run as unsplit generic sub-problems.
 //
 // Replaces the reference's cuBLAS call sites (math_functions.cu:16-65,
 // conv_layer.cu:25-121, inner_product_layer.cu:18-63).
@@ -195,6 +212,15 @@ struct GatherWalk {
   }
 };
 
+// matching read-side XOR for glds-staged tiles: element offset within a
+// linear [row][BK] image whose 16 B slots are swizzled by row
+template <typename T>
+__device__ inline int glds_col(int row, int col) {
+  constexpr int EPB = 16 / (int)sizeof(T);
+  int slot = col / EPB;
+  return (slot ^ (((row >> 2) & 1) << 1)) * EPB + (col % EPB);
+}
+
 // Guarded scalar staging of a PARTIAL final K-tile into the glds-layout
 // image (zero-filled beyond k_end): lets a GEMM whose K is not a BK
 // multiple still take the glds path for the full tiles (AlexNet conv2's
@@ -204,24 +230,7 @@ template <typename T, int ROWS, bool GATHER = false>
 __device__ inline void stage_tail_linear(T* lds, const T* __restrict__ src,
                                          int64_t lda, int row0, int k0,
                                          int k_end, int tid,
-                                         const GatherDesc* ga = nullptr);
-
-// matching read-side XOR for glds-staged tiles: element offset within a
-// linear [row][BK] image whose 16 B slots are swizzled by row
-template <typename T>
-__device__ inline int glds_col(int row, int col) {
-  using TR = GemmTraits<T>;
-  constexpr int EPB = 16 / (int)sizeof(T);
-  constexpr int LPR = TR::BK / EPB;
-  int slot = col / EPB;
-  return (slot ^ (((row >> 2) & 1) << 1)) * EPB + (col % EPB);
-}
-
-template <typename T, int ROWS, bool GATHER>
-__device__ inline void stage_tail_linear(T* lds, const T* __restrict__ src,
-                                         int64_t lda, int row0, int k0,
-                                         int k_end, int tid,
-                                         const GatherDesc* ga) {
+                                         const GatherDesc* ga = nullptr) {
   using TR = GemmTraits<T>;
   constexpr int BK = TR::BK;
   const int rem = k_end - k0;
@@ -250,6 +259,18 @@ __device__ inline int lds_col(int row, int kk) {
   constexpr int GM = (TR::BK / TR::VEC) - 1;  // k-group mask
   int kg = kk >> TR::GSH;
   return (((kg ^ (row >> TR::GSH)) & GM) << TR::GSH) | (kk & (TR::VEC - 1));
+}
+
+// The three column layouts of a staged tile; fragment reads undo them.
+enum ColMap {
+  COL_PADDED,  // register-staged K-last: linear, rows padded to RS
+  COL_KMAJOR,  // register-staged K-major: lds_col swizzle, rows padded to RS
+  COL_GLDS,    // glds: glds_col swizzle, unpadded BK rows
+};
+template <typename T, ColMap MAP>
+__device__ inline int tile_col(int row, int col) {
+  if (MAP == COL_GLDS) return glds_col<T>(row, col);
+  return lds_col<T, MAP == COL_KMAJOR>(row, col);
 }
 
 // Staging, split into {issue global loads -> regs} and {write regs -> LDS}
@@ -331,7 +352,7 @@ struct Stager {
           v[i * TR::VEC + j] = val;
         }
       }
-    } else if (FASTI && interior) {
+    } else if (interior) {
       // K-major interior: VEC unguarded row-vector loads per block
       constexpr int BLK_M = ROWS / TR::VEC;
 #pragma unroll
@@ -410,227 +431,105 @@ struct Stager {
 
 // Tile geometry: BM x BN block tile, 4 waves arranged WGM x WGN, each wave
 // owns a (BM/WGM) x (BN/WGN) sub-tile as FM x FN fragments of 16x16.
-template <typename T, typename OUT, int BM, int BN, int WGM, int WGN,
-          bool A_KLAST, bool B_KLAST, bool HAS_BIAS, bool SPLITK,
-          bool GA = false, bool GB = false>
-__global__ __launch_bounds__(256)
-void gemm_kernel(const T* __restrict__ Abase, const T* __restrict__ Bbase,
-                 OUT* __restrict__ Cbase, const float* __restrict__ bias,
-                 int M, int N, int K,
-                 int64_t lda, int64_t ldb, int64_t ldc,
-                 int64_t strideA, int64_t strideB, int64_t strideC,
-                 float alpha, float beta,
-                 float* __restrict__ ws, int kchunk,
-                 GatherDesc ga_a = {}, GatherDesc ga_b = {},
-                 bool relu = false, int xcd2d = 0) {
+// (m0, n0) is the block tile's origin, (wm, wn) the wave sub-tile's origin
+// inside it. The parts below take these as plain ints: gathered into a
+// struct, the compiler staged K-last operands differently from the kernel
+// they were cut from (profiles/gemm_refactor.md).
+
+// One staged K-tile into the accumulators: per MFMA k-step, FM + FN fragment
+// reads and the FM x FN MFMA nest. RS is the images' row stride, MAPA / MAPB
+// their column layouts.
+template <typename T, int FM, int FN, int RS, ColMap MAPA, ColMap MAPB>
+__device__ inline void tile_mma(const T* al, const T* bl, int wm, int wn,
+                                int lane, f32x4 (&acc)[FM][FN]) {
   using TR = GemmTraits<T>;
-  constexpr int BK = TR::BK, RS = TR::RS;
-  constexpr int FM = BM / WGM / 16, FN = BN / WGN / 16;
-  static_assert(WGM * WGN == 4, "4 waves per block");
+#pragma unroll
+  for (int kk = 0; kk < TR::BK; kk += TR::KSTEP) {
+    typename TR::frag_t a_frag[FM], b_frag[FN];
+#pragma unroll
+    for (int f = 0; f < FM; ++f) {
+      int row = wm + f * 16 + (lane & 15);
+      int col = kk + (lane >> 4) * (TR::KSTEP / 4);
+      a_frag[f] = *reinterpret_cast<const typename TR::frag_t*>(
+          &al[row * RS + tile_col<T, MAPA>(row, col)]);
+    }
+#pragma unroll
+    for (int f = 0; f < FN; ++f) {
+      int row = wn + f * 16 + (lane & 15);
+      int col = kk + (lane >> 4) * (TR::KSTEP / 4);
+      b_frag[f] = *reinterpret_cast<const typename TR::frag_t*>(
+          &bl[row * RS + tile_col<T, MAPB>(row, col)]);
+    }
+#pragma unroll
+    for (int fm = 0; fm < FM; ++fm)
+#pragma unroll
+      for (int fn = 0; fn < FN; ++fn)
+        acc[fm][fn] = TR::mfma(a_frag[fm], b_frag[fn], acc[fm][fn]);
+  }
+}
 
-  // T1 XCD-aware swizzle: the dispatcher places linear block b on XCD b%8
-  // (each with a private 4 MiB L2); consecutive tiles share A/B panels, so
-  // give each XCD a CONTIGUOUS run of tiles instead of a round-robin comb.
-  // Bijective only when the flattened grid is a multiple of 8 -- identity
-  // otherwise. z (split-K slice / batch) folds into the flatten so the
-  // remap stays a permutation of the whole grid.
-  int bx = blockIdx.x, by = blockIdx.y, bz = blockIdx.z;
-  if (xcd2d != 0) {
-    // 2D XCD super-tiling for re-read-bound grids (small K, many tiles --
-    // the fc-wgrad class: fc6 dW is 4096x9216x256, each A panel re-read
-    // by 72 tile columns and each B panel by 32 rows from HBM/L3). Each
-    // XCD owns an ry x cx RECTANGLE of tiles whose A+B panels fit its
-    // 4 MiB L2, so panel re-reads inside the rectangle are L2 hits.
-    // launch side guarantees nby % ry == 0, nbx % cx == 0 and
-    // (nby/ry)*(nbx/cx) == 8; grid.z is 1 for this class.
-    const int ry = xcd2d >> 16, cx = xcd2d & 0xFFFF;
-    const int nbx = gridDim.x;
-    const int regs_x = nbx / cx;
-    int64_t l = ((int64_t)bz * gridDim.y + by) * nbx + bx;
-    const int k = (int)(l & 7);
-    int64_t j = l >> 3;
-    bx = (k % regs_x) * cx + (int)(j % cx);
-    by = (k / regs_x) * ry + (int)(j / cx);
-    bz = 0;
+// glds main loop: full BK tiles via glds, one tile ahead of the MFMAs; a
+// partial final tile (K % BK != 0) is staged by guarded scalar writes into
+// the same swizzled image. a_lds / b_lds hold two buffers of BUF_A / BUF_B
+// elements each.
+template <typename T, int BM, int BN, int FM, int FN, bool GA, int BUF_A,
+          int BUF_B>
+__device__ inline void mainloop_glds(const T* A, const T* B, int64_t lda,
+                                     int64_t ldb, const GatherDesc& ga_a,
+                                     T* a_lds, T* b_lds, int m0, int n0,
+                                     int k_begin, int k_end, int tid,
+                                     int lane, int wid, int wm, int wn,
+                                     f32x4 (&acc)[FM][FN]) {
+  constexpr int BK = GemmTraits<T>::BK;
+  const int k_full = k_begin + ((k_end - k_begin) / BK) * BK;
+  T* a_lin0 = a_lds;
+  T* b_lin0 = b_lds;
+  T* a_lin1 = a_lds + BUF_A;
+  T* b_lin1 = b_lds + BUF_B;
+  GatherWalk<T, BM> walk;  // GA only
+  if constexpr (GA) {
+    walk.init(ga_a, m0, k_begin, wid, lane);
+    walk.stage(a_lin0, ga_a, wid);
   } else {
-    const int nbx = gridDim.x, nby = gridDim.y;
-    const int64_t nwg = (int64_t)nbx * nby * gridDim.z;
-    if ((nwg & 7) == 0 && nwg > 8) {
-      int64_t id = ((int64_t)bz * nby + by) * nbx + bx;
-      const int64_t cpx = nwg >> 3;
-      id = (id & 7) * cpx + (id >> 3);
-      bx = (int)(id % nbx);
-      by = (int)((id / nbx) % nby);
-      bz = (int)(id / ((int64_t)nbx * nby));
-    }
+    stage_glds<T, BM>(a_lin0, A, lda, m0, k_begin, wid, lane);
   }
-
-  // split-K: grid.z indexes the K-slice (batch must be 1); otherwise batch
-  const T* A = Abase + (SPLITK ? 0 : (int64_t)bz * strideA);
-  const T* B = Bbase + (SPLITK ? 0 : (int64_t)bz * strideB);
-  OUT* C = Cbase + (SPLITK ? 0 : (int64_t)bz * strideC);
-  int k_begin = 0, k_end = K;
-  if (SPLITK) {
-    k_begin = bz * kchunk;
-    k_end = min(K, k_begin + kchunk);
-  }
-
-  __shared__ __attribute__((aligned(16))) T a_lds[2][BM * RS];
-  __shared__ __attribute__((aligned(16))) T b_lds[2][BN * RS];
-
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wid = tid >> 6;
-  const int wm = (wid / WGN) * (BM / WGM);  // wave row offset in block tile
-  const int wn = (wid % WGN) * (BN / WGN);
-  const int m0 = by * BM;
-  const int n0 = bx * BN;
-
-  f32x4 acc[FM][FN] = {};
-
-  // glds fast path: interior tile, K-span a multiple of BK, vector-aligned
-  // rows (guide §5: direct-to-LDS staging removes the VGPR round trip and
-  // its VALU address work; edge tiles keep the guarded register pipeline)
-  {
-    constexpr int EPB = 16 / (int)sizeof(T);
-    const int k_span = k_end - k_begin;
-    bool glds_ok = A_KLAST && B_KLAST && (m0 + BM <= M) &&
-                   (n0 + BN <= N) && k_span >= BK &&
-                   (ldb % EPB) == 0 && (k_begin % EPB) == 0 &&
-                   (((uintptr_t)B & 15) == 0);
-    if (GA) {
-      // gathered A: every 16 B lane chunk must stay inside one cg run
-      // (chunk starts are EPB-aligned, so Cg % EPB suffices -- the old
-      // Cg % BK gate was overly strict and pushed grouped convs like
-      // AlexNet conv2 (Cg=48) onto the guarded register-gather path)
-      glds_ok = glds_ok && (ga_a.Cg % EPB) == 0 && (ga_a.C % EPB) == 0 &&
-                (ga_a.c0 % EPB) == 0;
-    } else {
-      glds_ok = glds_ok && (lda % EPB) == 0 && (((uintptr_t)A & 15) == 0);
-    }
-    if (glds_ok) {
-      // full BK tiles via glds; a partial final tile (K % BK != 0) is
-      // staged by guarded scalar writes into the same swizzled image
-      const int k_full = k_begin + (k_span / BK) * BK;
-      T* a_lin0 = a_lds[0];
-      T* b_lin0 = b_lds[0];
-      T* a_lin1 = a_lds[1];
-      T* b_lin1 = b_lds[1];
-      GatherWalk<T, BM> walk;  // GA only
-      if constexpr (GA) {
-        walk.init(ga_a, m0, k_begin, wid, lane);
-        walk.stage(a_lin0, ga_a, wid);
-      } else {
-        stage_glds<T, BM>(a_lin0, A, lda, m0, k_begin, wid, lane);
-      }
-      stage_glds<T, BN>(b_lin0, B, ldb, n0, k_begin, wid, lane);
-      __syncthreads();  // drains the in-flight glds (vmcnt 0) + barrier
-      int cur2 = 0;
-      for (int k0 = k_begin; k0 < k_end; k0 += BK) {
-        if (k0 + BK < k_full) {
-          // consecutive full tiles: the walk's tap sits at k0 + BK
-          if constexpr (GA)
-            walk.stage(cur2 ? a_lin0 : a_lin1, ga_a, wid);
-          else
-            stage_glds<T, BM>(cur2 ? a_lin0 : a_lin1, A, lda, m0, k0 + BK,
-                              wid, lane);
-          stage_glds<T, BN>(cur2 ? b_lin0 : b_lin1, B, ldb, n0, k0 + BK, wid,
-                            lane);
-        } else if (k0 + BK < k_end) {
-          stage_tail_linear<T, BM, GA>(cur2 ? a_lin0 : a_lin1, A, lda, m0,
-                                       k0 + BK, k_end, tid, &ga_a);
-          stage_tail_linear<T, BN, false>(cur2 ? b_lin0 : b_lin1, B, ldb, n0,
-                                          k0 + BK, k_end, tid, nullptr);
-        }
-        const T* al = cur2 ? a_lin1 : a_lin0;
-        const T* bl = cur2 ? b_lin1 : b_lin0;
-#pragma unroll
-        for (int kk = 0; kk < BK; kk += TR::KSTEP) {
-          typename TR::frag_t a_frag[FM], b_frag[FN];
-#pragma unroll
-          for (int f = 0; f < FM; ++f) {
-            int row = wm + f * 16 + (lane & 15);
-            int col = kk + (lane >> 4) * (TR::KSTEP / 4);
-            a_frag[f] = *reinterpret_cast<const typename TR::frag_t*>(
-                &al[row * BK + glds_col<T>(row, col)]);
-          }
-#pragma unroll
-          for (int f = 0; f < FN; ++f) {
-            int row = wn + f * 16 + (lane & 15);
-            int col = kk + (lane >> 4) * (TR::KSTEP / 4);
-            b_frag[f] = *reinterpret_cast<const typename TR::frag_t*>(
-                &bl[row * BK + glds_col<T>(row, col)]);
-          }
-#pragma unroll
-          for (int fm = 0; fm < FM; ++fm)
-#pragma unroll
-            for (int fn = 0; fn < FN; ++fn)
-              acc[fm][fn] = TR::mfma(a_frag[fm], b_frag[fn], acc[fm][fn]);
-        }
-        __syncthreads();
-        cur2 ^= 1;
-      }
-      goto epilogue;
-    }
-  }
-  {
-  Stager<T, BM, A_KLAST, GA, SPLITK> sa;
-  Stager<T, BN, B_KLAST, GB, SPLITK> sb;
-  // prologue: tile 0 -> LDS[0]; issue tile 1 loads
-  sa.load(A, lda, m0, M, k_begin, k_end, tid, &ga_a);
-  sb.load(B, ldb, n0, N, k_begin, k_end, tid, &ga_b);
-  sa.write(a_lds[0], tid);
-  sb.write(b_lds[0], tid);
-  if (k_begin + BK < k_end) {
-    sa.load(A, lda, m0, M, k_begin + BK, k_end, tid, &ga_a);
-    sb.load(B, ldb, n0, N, k_begin + BK, k_end, tid, &ga_b);
-  }
-  __syncthreads();
-
+  stage_glds<T, BN>(b_lin0, B, ldb, n0, k_begin, wid, lane);
+  __syncthreads();  // drains the in-flight glds (vmcnt 0) + barrier
   int cur = 0;
   for (int k0 = k_begin; k0 < k_end; k0 += BK) {
-    // regs hold tile t+1: write it into the other LDS buffer, then issue
-    // tile t+2's loads so they fly during this tile's MFMA phase
-    if (k0 + BK < k_end) {
-      sa.write(a_lds[cur ^ 1], tid);
-      sb.write(b_lds[cur ^ 1], tid);
-      if (k0 + 2 * BK < k_end) {
-        sa.load(A, lda, m0, M, k0 + 2 * BK, k_end, tid, &ga_a);
-        sb.load(B, ldb, n0, N, k0 + 2 * BK, k_end, tid, &ga_b);
-      }
+    if (k0 + BK < k_full) {
+      // consecutive full tiles: the walk's tap sits at k0 + BK
+      if constexpr (GA)
+        walk.stage(cur ? a_lin0 : a_lin1, ga_a, wid);
+      else
+        stage_glds<T, BM>(cur ? a_lin0 : a_lin1, A, lda, m0, k0 + BK, wid,
+                          lane);
+      stage_glds<T, BN>(cur ? b_lin0 : b_lin1, B, ldb, n0, k0 + BK, wid,
+                        lane);
+    } else if (k0 + BK < k_end) {
+      stage_tail_linear<T, BM, GA>(cur ? a_lin0 : a_lin1, A, lda, m0,
+                                   k0 + BK, k_end, tid, &ga_a);
+      stage_tail_linear<T, BN, false>(cur ? b_lin0 : b_lin1, B, ldb, n0,
+                                      k0 + BK, k_end, tid, nullptr);
     }
-
-#pragma unroll
-    for (int kk = 0; kk < BK; kk += TR::KSTEP) {
-      typename TR::frag_t a_frag[FM], b_frag[FN];
-#pragma unroll
-      for (int f = 0; f < FM; ++f) {
-        int row = wm + f * 16 + (lane & 15);
-        int col = kk + (lane >> 4) * (TR::KSTEP / 4);
-        a_frag[f] = *reinterpret_cast<const typename TR::frag_t*>(
-            &a_lds[cur][row * RS + lds_col<T, !A_KLAST>(row, col)]);
-      }
-#pragma unroll
-      for (int f = 0; f < FN; ++f) {
-        int row = wn + f * 16 + (lane & 15);
-        int col = kk + (lane >> 4) * (TR::KSTEP / 4);
-        b_frag[f] = *reinterpret_cast<const typename TR::frag_t*>(
-            &b_lds[cur][row * RS + lds_col<T, !B_KLAST>(row, col)]);
-      }
-#pragma unroll
-      for (int fm = 0; fm < FM; ++fm)
-#pragma unroll
-        for (int fn = 0; fn < FN; ++fn)
-          acc[fm][fn] = TR::mfma(a_frag[fm], b_frag[fn], acc[fm][fn]);
-    }
+    tile_mma<T, FM, FN, BK, COL_GLDS, COL_GLDS>(
+        cur ? a_lin1 : a_lin0, cur ? b_lin1 : b_lin0, wm, wn, lane, acc);
     __syncthreads();
     cur ^= 1;
   }
-  }
+}
 
-epilogue:
-  // Epilogue: C/D fragment map for 16x16 shapes: col = lane&15,
-  // row = (lane>>4)*4 + r (guide §3; dtype-independent on gfx950).
+// Epilogue: C/D fragment map for 16x16 shapes: col = lane&15,
+// row = (lane>>4)*4 + r (guide §3; dtype-independent on gfx950).
+// bz is the split-K slice (the workspace slab it writes).
+template <typename OUT, int FM, int FN, bool HAS_BIAS, bool SPLITK>
+__device__ inline void gemm_epilogue(const f32x4 (&acc)[FM][FN],
+                                     OUT* __restrict__ C,
+                                     const float* __restrict__ bias,
+                                     float* __restrict__ ws, int M, int N,
+                                     int64_t ldc, float alpha, float beta,
+                                     bool relu, int bz, int m0, int n0,
+                                     int wm, int wn, int lane) {
 #pragma unroll
   for (int fm = 0; fm < FM; ++fm) {
 #pragma unroll
@@ -662,6 +561,115 @@ epilogue:
       }
     }
   }
+}
+
+// xcd2d: the plan's 2D-XCD rectangle as (ry << 16) | cx, 0 for none
+template <typename T, typename OUT, int BM, int BN, int WGM, int WGN,
+          bool A_KLAST, bool B_KLAST, bool HAS_BIAS, bool SPLITK,
+          bool GA = false, bool GB = false>
+__global__ __launch_bounds__(256)
+void gemm_kernel(const T* __restrict__ A, const T* __restrict__ B,
+                 OUT* __restrict__ C, const float* __restrict__ bias,
+                 int M, int N, int K,
+                 int64_t lda, int64_t ldb, int64_t ldc,
+                 float alpha, float beta,
+                 float* __restrict__ ws, int kchunk,
+                 GatherDesc ga_a = {}, GatherDesc ga_b = {},
+                 bool relu = false, int xcd2d = 0) {
+  using TR = GemmTraits<T>;
+  constexpr int BK = TR::BK, RS = TR::RS;
+  constexpr int FM = BM / WGM / 16, FN = BN / WGN / 16;
+  static_assert(WGM * WGN == 4, "4 waves per block");
+
+  const GemmBlock blk =
+      xcd2d != 0 ? ps_remap_rect(gridDim.x, xcd2d >> 16, xcd2d & 0xFFFF,
+                                 blockIdx.x, blockIdx.y)
+                 : ps_remap_linear(gridDim.x, gridDim.y, gridDim.z,
+                                   blockIdx.x, blockIdx.y, blockIdx.z);
+
+  __shared__ __attribute__((aligned(16))) T a_lds[2][BM * RS];
+  __shared__ __attribute__((aligned(16))) T b_lds[2][BN * RS];
+
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wid = tid >> 6;
+  const int wm = (wid / WGN) * (BM / WGM);  // wave row offset in block tile
+  const int wn = (wid % WGN) * (BN / WGN);
+  const int m0 = blk.by * BM;
+  const int n0 = blk.bx * BN;
+  // split-K: grid.z indexes the K slice
+  int k_begin = 0, k_end = K;
+  if (SPLITK) {
+    k_begin = blk.bz * kchunk;
+    k_end = min(K, k_begin + kchunk);
+  }
+
+  f32x4 acc[FM][FN] = {};
+
+  // glds fast path: interior tile, K-span a multiple of BK, vector-aligned
+  // rows (guide §5: direct-to-LDS staging removes the VGPR round trip and
+  // its VALU address work; edge tiles keep the guarded register pipeline)
+  constexpr int EPB = 16 / (int)sizeof(T);
+  bool glds_ok = A_KLAST && B_KLAST && (m0 + BM <= M) &&
+                 (n0 + BN <= N) && k_end - k_begin >= BK &&
+                 (ldb % EPB) == 0 && (k_begin % EPB) == 0 &&
+                 (((uintptr_t)B & 15) == 0);
+  if (GA) {
+    // gathered A: every 16 B lane chunk must stay inside one cg run
+    // (chunk starts are EPB-aligned, so Cg % EPB suffices -- the old
+    // Cg % BK gate was overly strict and pushed grouped convs like
+    // AlexNet conv2 (Cg=48) onto the guarded register-gather path)
+    glds_ok = glds_ok && (ga_a.Cg % EPB) == 0 && (ga_a.C % EPB) == 0 &&
+              (ga_a.c0 % EPB) == 0;
+  } else {
+    glds_ok = glds_ok && (lda % EPB) == 0 && (((uintptr_t)A & 15) == 0);
+  }
+  if (glds_ok) {
+    mainloop_glds<T, BM, BN, FM, FN, GA, BM * RS, BN * RS>(
+        A, B, lda, ldb, ga_a, a_lds[0], b_lds[0], m0, n0, k_begin, k_end, tid,
+        lane, wid, wm, wn, acc);
+  } else {
+    // Register-staged main loop: guarded loads for every tile the glds loop
+    // cannot take (edge tiles, K-major operands, unaligned rows). It stays
+    // in the kernel body: as a function of its own the compiler merges two of
+    // the three staging-load sites of the K-major kernels and drains them
+    // with more waits (fp32 4096x9216x256 K-major x K-major: 95 -> 80 TF/s,
+    // profiles/gemm_refactor.md).
+    Stager<T, BM, A_KLAST, GA, SPLITK> sa;
+    Stager<T, BN, B_KLAST, GB, SPLITK> sb;
+    // prologue: tile 0 -> LDS[0]; issue tile 1 loads
+    sa.load(A, lda, m0, M, k_begin, k_end, tid, &ga_a);
+    sb.load(B, ldb, n0, N, k_begin, k_end, tid, &ga_b);
+    sa.write(a_lds[0], tid);
+    sb.write(b_lds[0], tid);
+    if (k_begin + BK < k_end) {
+      sa.load(A, lda, m0, M, k_begin + BK, k_end, tid, &ga_a);
+      sb.load(B, ldb, n0, N, k_begin + BK, k_end, tid, &ga_b);
+    }
+    __syncthreads();
+
+    int cur = 0;
+    for (int k0 = k_begin; k0 < k_end; k0 += BK) {
+      // regs hold tile t+1: write it into the other LDS buffer, then issue
+      // tile t+2's loads so they fly during this tile's MFMA phase
+      if (k0 + BK < k_end) {
+        sa.write(a_lds[cur ^ 1], tid);
+        sb.write(b_lds[cur ^ 1], tid);
+        if (k0 + 2 * BK < k_end) {
+          sa.load(A, lda, m0, M, k0 + 2 * BK, k_end, tid, &ga_a);
+          sb.load(B, ldb, n0, N, k0 + 2 * BK, k_end, tid, &ga_b);
+        }
+      }
+      tile_mma<T, FM, FN, RS, A_KLAST ? COL_PADDED : COL_KMAJOR,
+               B_KLAST ? COL_PADDED : COL_KMAJOR>(a_lds[cur], b_lds[cur], wm,
+                                                  wn, lane, acc);
+      __syncthreads();
+      cur ^= 1;
+    }
+  }
+  gemm_epilogue<OUT, FM, FN, HAS_BIAS, SPLITK>(acc, C, bias, ws, M, N, ldc,
+                                               alpha, beta, relu, blk.bz, m0,
+                                               n0, wm, wn, lane);
 }
 
 // combine split-K partial slabs: C = alpha*sum_s ws[s] + bias + beta*C
@@ -867,38 +875,11 @@ void gemm_tn_tr_kernel(const __bf16* __restrict__ A,
   static_assert(WGM2 * WGN2 == 4, "4 waves");
   __shared__ __attribute__((aligned(16))) __bf16 a_lds[2][64 * BM2];
   __shared__ __attribute__((aligned(16))) __bf16 b_lds[2][64 * BN2];
-  int bx = blockIdx.x, by = blockIdx.y, bz = blockIdx.z;
-  {
-    const int nbx = gridDim.x, nby = gridDim.y;
-    const int64_t G = (int64_t)nby * gridDim.z;  // (by, bz) groups
-    if (SPLITK && (G & 7) == 0 && G >= 8) {
-      // L2-reuse placement: all nbx tiles of one (by, bz) group -- they
-      // stage the SAME A k-slice (bm x kchunk, a few MB) -- land on ONE
-      // XCD so the re-reads hit that XCD's 4 MiB L2 (34.5 TB/s aggregate)
-      // instead of HBM. The hardware dispatcher places linear id l on XCD
-      // l%8, so group g goes to XCD g%8 and its tiles get consecutive
-      // slots there. (The launcher pads gridDim.z until nby*nbz % 8 == 0;
-      // padded bz exits via the k_begin >= k_end guard below.)
-      int64_t l = ((int64_t)blockIdx.z * nby + blockIdx.y) * nbx + blockIdx.x;
-      const int xcd = (int)(l & 7);
-      int64_t j = l >> 3;
-      bx = (int)(j % nbx);
-      int g2 = (int)((j / nbx) * 8 + xcd);
-      by = g2 % nby;
-      bz = g2 / nby;
-    } else {
-      // T1 XCD swizzle (same as gemm_kernel)
-      const int64_t nwg = (int64_t)nbx * nby * gridDim.z;
-      if ((nwg & 7) == 0 && nwg > 8) {
-        int64_t id = ((int64_t)bz * nby + by) * nbx + bx;
-        const int64_t cpx = nwg >> 3;
-        id = (id & 7) * cpx + (id >> 3);
-        bx = (int)(id % nbx);
-        by = (int)((id / nbx) % nby);
-        bz = (int)(id / ((int64_t)nbx * nby));
-      }
-    }
-  }
+  // (by, bz) groups clustered per XCD when split, else the linear swizzle;
+  // a padded bz exits via the k_begin >= k_end guard below
+  const GemmBlock blk = ps_remap_tr(SPLITK, gridDim.x, gridDim.y, gridDim.z,
+                                    blockIdx.x, blockIdx.y, blockIdx.z);
+  const int bx = blk.bx, by = blk.by, bz = blk.bz;
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -1006,24 +987,14 @@ void gemm_tn_tr_kernel(const __bf16* __restrict__ A,
 }
 
 // ---------------------------------------------------------------------------
-// planning: path choice and split-K policy for one GEMM, made once
-// (ps_gemm_plan) and executed as planned (ps_gemm_run)
+// planning (ps_gemm_plan) and launching as planned (ps_gemm_run)
 // ---------------------------------------------------------------------------
-
-// what the generic launchers run: the problem plus the plan's split-K
-struct GemmLaunch : GemmArgs {
-  float* ws;   // split-K partials (splitk * M * N floats) or null: atomic
-  int splitk;  // > 1 needs batch == 1
-};
-
-template <typename T, typename OUT>
-static void gemm_dispatch(const GemmLaunch& g, hipStream_t s);
 
 // Atomic split-K adds into C, which the launcher zeroes as ONE contiguous
 // M*N block: only when nothing else lands in C and its rows are dense.
 static bool atomic_splitk_ok(const GemmArgs& g) {
   return g.out_f32 && g.bias == nullptr && g.beta == 0.0f && !g.relu &&
-         g.batch == 1 && g.ldc == g.N;
+         g.ldc == g.N;
 }
 
 // Operand eligibility for the tr16 TN path: what ps_gemm_plan.h cannot see
@@ -1031,7 +1002,7 @@ static bool atomic_splitk_ok(const GemmArgs& g) {
 static bool tn_tr_operands_ok(const GemmArgs& g) {
   if (!g.in_bf16 || !g.out_f32) return false;
   if (g.a_klast || g.b_klast || g.gather_a) return false;
-  if (g.bias || g.relu || g.beta != 0.0f || g.batch > 1) return false;
+  if (g.bias || g.relu || g.beta != 0.0f) return false;
   if (g.lda % 8) return false;
   if ((uintptr_t)g.A & 15) return false;
   if (g.gather_b) {
@@ -1041,6 +1012,21 @@ static bool tn_tr_operands_ok(const GemmArgs& g) {
     if (g.ldb % 8 || ((uintptr_t)g.B & 15)) return false;
   }
   return true;
+}
+
+static GemmShape gemm_shape(const GemmArgs& g) {
+  GemmShape sh;
+  sh.M = g.M;
+  sh.N = g.N;
+  sh.K = g.K;
+  sh.esize = g.in_bf16 ? (int)sizeof(__bf16) : (int)sizeof(float);
+  sh.bk = g.in_bf16 ? GemmTraits<__bf16>::BK : GemmTraits<float>::BK;
+  sh.atomic_ok = atomic_splitk_ok(g);
+  sh.tr_ok = tn_tr_operands_ok(g);
+  sh.gather_b = g.gather_b != nullptr;
+  sh.nt = g.a_klast && g.b_klast;
+  sh.only128 = !g.a_klast && g.b_klast;
+  return sh;
 }
 
 // tests / tuning only (ps_gemm_set_tr_tune); all zero in the training path
@@ -1055,179 +1041,171 @@ static void zero_c_for_atomics(const GemmArgs& g, hipStream_t s) {
     (void)hipMemsetAsync(g.C, 0, (size_t)g.M * g.N * sizeof(float), s);
 }
 
-static void run_gemm_tn_tr(const GemmArgs& g, const GemmPlan& p,
-                           hipStream_t s) {
-  const int M0 = p.M0, N0 = p.N0, bm = p.bm, bn = p.bn, sk = p.splitk;
-  const int kchunk = p.kchunk;
-  const int skz = ps_tr_grid_z(p);  // padded: enables L2 clustering
-  if (sk > 1) zero_c_for_atomics(g, s);
-  // ceil: a bn = 128 grid runs its last column tile ragged (N0 % 64 == 0)
-  dim3 grid((N0 + bn - 1) / bn, M0 / bm, skz);
-  GatherDesc gb = g.gather_b ? *g.gather_b : GatherDesc{};
-#define PS_TR_LAUNCH(BM_, BN_, WGM_, WGN_)                                  \
-  do {                                                                      \
-    if (g.gather_b) {                                                       \
-      if (sk > 1)                                                           \
-        gemm_tn_tr_kernel<BM_, BN_, WGM_, WGN_, true, true>                 \
-            <<<grid, 256, 0, s>>>((const __bf16*)g.A, (const __bf16*)g.B,   \
-                                  (float*)g.C, M0, N0, g.K, g.lda,          \
-                                  g.ldb, g.ldc, g.alpha, kchunk, gb);       \
-      else                                                                  \
-        gemm_tn_tr_kernel<BM_, BN_, WGM_, WGN_, false, true>                \
-            <<<grid, 256, 0, s>>>((const __bf16*)g.A, (const __bf16*)g.B,   \
-                                  (float*)g.C, M0, N0, g.K, g.lda,          \
-                                  g.ldb, g.ldc, g.alpha, kchunk, gb);       \
-    } else if (sk > 1)                                                      \
-      gemm_tn_tr_kernel<BM_, BN_, WGM_, WGN_, true><<<grid, 256, 0, s>>>(   \
-          (const __bf16*)g.A, (const __bf16*)g.B, (float*)g.C, M0, N0,      \
-          g.K, g.lda, g.ldb, g.ldc, g.alpha, kchunk);                       \
-    else                                                                    \
-      gemm_tn_tr_kernel<BM_, BN_, WGM_, WGN_, false><<<grid, 256, 0, s>>>(  \
-          (const __bf16*)g.A, (const __bf16*)g.B, (float*)g.C, M0, N0,      \
-          g.K, g.lda, g.ldb, g.ldc, g.alpha, kchunk);                       \
-  } while (0)
-#define PS_TR_CASE(BM_, BN_, WGM_, WGN_) \
-  if (bm == BM_ && bn == BN_) PS_TR_LAUNCH(BM_, BN_, WGM_, WGN_); else
-  PS_TR_TILE_LIST(PS_TR_CASE) {
-    fprintf(stderr, "tr16 gemm: no %dx%d tile\n", bm, bn);
-    abort();
-  }
-#undef PS_TR_CASE
-#undef PS_TR_LAUNCH
-  // edge strips [0,M) x [N0,N) and [M0,M) x [0,N0): generic kernel, unsplit
-  // (plain stores over the zeroed C)
-  if (N0 != g.N) {
-    GemmLaunch gt = {g, nullptr, 1};
-    gt.N = g.N - N0;
-    gt.B = (const void*)((const __bf16*)g.B + N0);
-    gt.C = (void*)((float*)g.C + N0);
-    gemm_dispatch<__bf16, float>(gt, s);
-  }
-  if (M0 != g.M) {
-    GemmLaunch gt = {g, nullptr, 1};
-    gt.M = g.M - M0; gt.N = N0;
-    gt.A = (const void*)((const __bf16*)g.A + M0);
-    gt.C = (void*)((float*)g.C + (int64_t)M0 * g.ldc);
-    gemm_dispatch<__bf16, float>(gt, s);
-  }
+// run-time bool -> template argument: f(std::true_type{} / std::false_type{})
+template <typename F>
+static void with_bool(bool b, F&& f) {
+  if (b) f(std::true_type{});
+  else f(std::false_type{});
 }
 
-// ---------------------------------------------------------------------------
-// launchers
-// ---------------------------------------------------------------------------
-
+// The launchers decide nothing: grid and kernel arguments come from the plan.
 template <typename T, typename OUT, int BM, int BN, int WGM, int WGN,
-          bool AK, bool BK_, bool HB, bool GA = false, bool GB = false>
-static void launch_tile(const GemmLaunch& g, hipStream_t s) {
+          bool AK, bool BK_, bool HB, bool GA, bool GB>
+static void launch_tile(const GemmArgs& g, const GemmPlan& p, float* ws,
+                        hipStream_t s) {
   GatherDesc da = GA ? *g.gather_a : GatherDesc{};
   GatherDesc db = GB ? *g.gather_b : GatherDesc{};
-  const bool sk = g.splitk > 1;
-  dim3 grid(cdiv(g.N, BN), cdiv(g.M, BM), sk ? g.splitk : g.batch);
-  dim3 block(256);
-  int kchunk = 0;
-  if (sk) {
-    constexpr int TBK = GemmTraits<T>::BK;
-    kchunk = cdiv(cdiv(g.K, g.splitk), TBK) * TBK;
-  }
-  // 2D XCD clustering: re-read-bound shallow-K grids with full tiles
-  int xcd2d = 0;
-  if (!sk && g.batch == 1 && g.K <= 1024 && g.M % BM == 0 && g.N % BN == 0) {
-    const int nby = g.M / BM, nbx = g.N / BN;
-    if ((int64_t)nby * nbx >= 512) {
-      // pick (ry, cx): ry | nby, cx | nbx, (nby/ry)*(nbx/cx) == 8,
-      // minimizing the L2 working set ry*BM + cx*BN (K common factor)
-      int64_t best = -1;
-      for (int gy = 1; gy <= 8; gy <<= 1) {
-        const int gx = 8 / gy;
-        if (nby % gy || nbx % gx) continue;
-        const int ry = nby / gy, cx = nbx / gx;
-        const int64_t ws_bytes =
-            ((int64_t)ry * BM + (int64_t)cx * BN) * g.K * (int64_t)sizeof(T);
-        if (ws_bytes > (3LL << 20)) continue;  // must fit the 4 MiB L2
-        if (best < 0 || ws_bytes < best) {
-          best = ws_bytes;
-          xcd2d = (ry << 16) | cx;
-        }
-      }
-    }
-  }
-  if (sk) {
-    gemm_kernel<T, OUT, BM, BN, WGM, WGN, AK, BK_, HB, true, GA, GB>
-        <<<grid, block, 0, s>>>(
-            (const T*)g.A, (const T*)g.B, (OUT*)g.C, g.bias, g.M, g.N, g.K,
-            g.lda, g.ldb, g.ldc, g.strideA, g.strideB, g.strideC, g.alpha,
-            g.beta, (float*)g.ws, kchunk, da, db, g.relu);
-    if (!g.ws) return;  // atomic split-K accumulated into C directly
-    int64_t MN = (int64_t)g.M * g.N;
-    int64_t rb = cdiv64(MN, 256);
-    if (rb > 2048) rb = 2048;
-    if (HB)
-      splitk_reduce_k<OUT, true><<<dim3((unsigned)rb), 256, 0, s>>>(
-          (const float*)g.ws, (OUT*)g.C, g.bias, g.M, g.N, g.ldc, g.splitk,
-          g.alpha, g.beta, g.relu);
-    else
-      splitk_reduce_k<OUT, false><<<dim3((unsigned)rb), 256, 0, s>>>(
-          (const float*)g.ws, (OUT*)g.C, g.bias, g.M, g.N, g.ldc, g.splitk,
-          g.alpha, g.beta, g.relu);
-  } else {
-    gemm_kernel<T, OUT, BM, BN, WGM, WGN, AK, BK_, HB, false, GA, GB>
-        <<<grid, block, 0, s>>>(
-            (const T*)g.A, (const T*)g.B, (OUT*)g.C, g.bias, g.M, g.N, g.K,
-            g.lda, g.ldb, g.ldc, g.strideA, g.strideB, g.strideC, g.alpha,
-            g.beta, nullptr, 0, da, db, g.relu, xcd2d);
-  }
+  dim3 grid(cdiv(g.N, BN), cdiv(g.M, BM), p.splitk);
+  with_bool(p.splitk > 1, [&](auto sk) {
+    gemm_kernel<T, OUT, BM, BN, WGM, WGN, AK, BK_, HB, decltype(sk)::value,
+                GA, GB><<<grid, 256, 0, s>>>(
+        (const T*)g.A, (const T*)g.B, (OUT*)g.C, g.bias, g.M, g.N, g.K,
+        g.lda, g.ldb, g.ldc, g.alpha, g.beta, ws, p.kchunk, da, db, g.relu,
+        (p.ry << 16) | p.cx);
+  });
+  if (p.splitk == 1 || !ws) return;  // atomic split-K accumulated into C
+  int64_t rb = cdiv64((int64_t)g.M * g.N, 256);
+  if (rb > 2048) rb = 2048;
+  splitk_reduce_k<OUT, HB><<<dim3((unsigned)rb), 256, 0, s>>>(
+      ws, (OUT*)g.C, g.bias, g.M, g.N, g.ldc, p.splitk, g.alpha, g.beta,
+      g.relu);
 }
 
-template <typename T, typename OUT, bool AK, bool BK_, bool HB,
-          bool GA = false, bool GB = false>
-static void dispatch_tiles(const GemmLaunch& g, hipStream_t s) {
-  int bm, bn;
-  pick_gemm_tile(g.M, g.N, &bm, &bn, AK && BK_);
-  if constexpr (AK && BK_) {
-    // the N-fitting tiles, built for K-last x K-last only (conv forward and
-    // dgrad, FC forward)
-    if (bm == 128 && bn == 96)
-      return launch_tile<T, OUT, 128, 96, 2, 2, AK, BK_, HB, GA, GB>(g, s);
-    if (bm == 128 && bn == 48)
-      return launch_tile<T, OUT, 128, 48, 4, 1, AK, BK_, HB, GA, GB>(g, s);
+static const char* dtype_name(bool bf16) { return bf16 ? "bf16" : "f32"; }
+
+static void die_not_built(const GemmArgs& g, const char* what) {
+  fprintf(stderr,
+          "gemm: %s: %s in, %s out, A %s%s, B %s%s%s is not instantiated\n",
+          what, dtype_name(g.in_bf16), dtype_name(!g.out_f32),
+          g.a_klast ? "K-last" : "K-major", g.gather_a ? " gathered" : "",
+          g.b_klast ? "K-last" : "K-major", g.gather_b ? " gathered" : "",
+          g.bias ? ", bias" : "");
+  abort();
+}
+
+// which tiles of PS_GEMM_TILE_LIST a layout is built for: the N-fitting
+// tiles for K-last x K-last only; A K-major x B K-last (test entry only)
+// for 128x128 only
+constexpr bool tile_built(int bm, int bn, bool narrow_only, bool ak,
+                          bool bk) {
+  return (!narrow_only || (ak && bk)) && (ak || !bk || (bm == 128 && bn == 128));
+}
+
+// WHAT IS INSTANTIATED follows what the run_gemm call sites in bindings.cpp
+// can produce. C has the input dtype in every forward and data-gradient
+// GEMM and is f32 in every weight gradient and in the test entry ext.gemm
+// (which has no bias and no gather). So:
+//   - a bias or a gathered A (forward / dgrad-as-forward) comes only with
+//     OUT == T;
+//   - a K-major A (weight gradients and gemm_at_b, gathered B included; the
+//     test entry) comes only with f32 out.
+// f32 x f32 satisfies both, bf16 -> bf16 and bf16 -> f32 one each. Anything
+// else aborts by name; so does a planned tile the layout is not built for.
+template <typename T, typename OUT, bool AK, bool BK_, bool HB, bool GA,
+          bool GB>
+static void dispatch_tiles(const GemmArgs& g, const GemmPlan& p, float* ws,
+                           hipStream_t s) {
+  constexpr bool same = std::is_same<T, OUT>::value;
+  constexpr bool f32out = std::is_same<OUT, float>::value;
+  if constexpr (((HB || GA) && !same) || (!AK && !f32out)) {
+    die_not_built(g, "dtype x layout x epilogue");
+  } else {
+#define PS_GEMM_CASE(BM_, BN_, WGM_, WGN_, NARROW_)                         \
+  if constexpr (tile_built(BM_, BN_, NARROW_, AK, BK_))                     \
+    if (p.bm == BM_ && p.bn == BN_)                                         \
+      return launch_tile<T, OUT, BM_, BN_, WGM_, WGN_, AK, BK_, HB, GA, GB>( \
+          g, p, ws, s);
+    PS_GEMM_TILE_LIST(PS_GEMM_CASE)
+#undef PS_GEMM_CASE
+    fprintf(stderr, "gemm: no %dx%d tile\n", p.bm, p.bn);
+    die_not_built(g, "tile");
   }
-  if (bm == 128 && bn == 32)
-    launch_tile<T, OUT, 128, 32, 4, 1, AK, BK_, HB, GA, GB>(g, s);
-  else if (bm == 32 && bn == 128)
-    launch_tile<T, OUT, 32, 128, 1, 4, AK, BK_, HB, GA, GB>(g, s);
-  else if (bm == 128 && bn == 16)
-    launch_tile<T, OUT, 128, 16, 4, 1, AK, BK_, HB, GA, GB>(g, s);
-  else if (bm == 16 && bn == 128)
-    launch_tile<T, OUT, 16, 128, 1, 4, AK, BK_, HB, GA, GB>(g, s);
-  else if (bm == 64 && bn == 64)
-    launch_tile<T, OUT, 64, 64, 2, 2, AK, BK_, HB, GA, GB>(g, s);
-  else
-    launch_tile<T, OUT, 128, 128, 2, 2, AK, BK_, HB, GA, GB>(g, s);
 }
 
 template <typename T, typename OUT>
-static void gemm_dispatch(const GemmLaunch& g, hipStream_t s) {
-  const bool hb = g.bias != nullptr;
-  if (g.a_klast && g.b_klast) {
-    if (g.gather_a) {
-      // implicit-GEMM conv forward: A rows gathered from NHWC x
-      if (hb) dispatch_tiles<T, OUT, true, true, true, true, false>(g, s);
-      else dispatch_tiles<T, OUT, true, true, false, true, false>(g, s);
-    } else if (hb) {
-      dispatch_tiles<T, OUT, true, true, true>(g, s);
-    } else {
-      dispatch_tiles<T, OUT, true, true, false>(g, s);
-    }
-  } else if (g.a_klast && !g.b_klast) {
-    dispatch_tiles<T, OUT, true, false, false>(g, s);
-  } else if (!g.a_klast && g.b_klast) {
-    // unused in the framework (kept for the generic test entry): 128x128 only
-    launch_tile<T, OUT, 128, 128, 2, 2, false, true, false>(g, s);
+static void gemm_dispatch(const GemmArgs& g, const GemmPlan& p, float* ws,
+                          hipStream_t s) {
+  const bool nt = g.a_klast && g.b_klast;
+  // bias and gathered A exist for K-last x K-last, gathered B for K-major x
+  // K-major
+  if (((g.bias || g.gather_a) && !nt) ||
+      (g.gather_b && (g.a_klast || g.b_klast)))
+    die_not_built(g, "layout");
+  if (nt) {
+    // forward GEMMs; gathered A: implicit-GEMM conv forward
+    with_bool(g.bias != nullptr, [&](auto hb) {
+      with_bool(g.gather_a != nullptr, [&](auto ga) {
+        dispatch_tiles<T, OUT, true, true, decltype(hb)::value,
+                       decltype(ga)::value, false>(g, p, ws, s);
+      });
+    });
+  } else if (g.a_klast) {
+    dispatch_tiles<T, OUT, true, false, false, false, false>(g, p, ws, s);
+  } else if (g.b_klast) {
+    // unused in the framework (kept for the generic test entry)
+    dispatch_tiles<T, OUT, false, true, false, false, false>(g, p, ws, s);
   } else {
-    if (g.gather_b)  // implicit-GEMM conv wgrad: K-major B gathered from x
-      dispatch_tiles<T, OUT, false, false, false, false, true>(g, s);
-    else
-      dispatch_tiles<T, OUT, false, false, false>(g, s);
+    // gathered B: implicit-GEMM conv wgrad, K-major B gathered from x
+    with_bool(g.gather_b != nullptr, [&](auto gb) {
+      dispatch_tiles<T, OUT, false, false, false, false,
+                     decltype(gb)::value>(g, p, ws, s);
+    });
+  }
+}
+
+static void run_gemm_generic(const GemmArgs& g, const GemmPlan& p, float* ws,
+                             hipStream_t s) {
+  if (p.ws_elems == 0) ws = nullptr;
+  if (p.splitk > 1 && !ws) zero_c_for_atomics(g, s);
+  if (!g.in_bf16) gemm_dispatch<float, float>(g, p, ws, s);
+  else if (g.out_f32) gemm_dispatch<__bf16, float>(g, p, ws, s);
+  else gemm_dispatch<__bf16, __bf16>(g, p, ws, s);
+}
+
+static void run_gemm_tn_tr(const GemmArgs& g, const GemmPlan& p,
+                           hipStream_t s) {
+  const int M0 = p.M0, N0 = p.N0;
+  if (p.splitk > 1) zero_c_for_atomics(g, s);
+  // ceil: a bn = 128 grid runs its last column tile ragged (N0 % 64 == 0);
+  // grid.z padded: enables L2 clustering
+  dim3 grid((N0 + p.bn - 1) / p.bn, M0 / p.bm, ps_tr_grid_z(p));
+  GatherDesc gb = g.gather_b ? *g.gather_b : GatherDesc{};
+#define PS_TR_CASE(BM_, BN_, WGM_, WGN_)                                    \
+  if (p.bm == BM_ && p.bn == BN_)                                           \
+    with_bool(p.splitk > 1, [&](auto sk) {                                  \
+      with_bool(g.gather_b != nullptr, [&](auto gat) {                      \
+        gemm_tn_tr_kernel<BM_, BN_, WGM_, WGN_, decltype(sk)::value,        \
+                          decltype(gat)::value><<<grid, 256, 0, s>>>(       \
+            (const __bf16*)g.A, (const __bf16*)g.B, (float*)g.C, M0, N0,    \
+            g.K, g.lda, g.ldb, g.ldc, g.alpha, p.kchunk, gb);               \
+      });                                                                   \
+    });                                                                     \
+  else
+  PS_TR_TILE_LIST(PS_TR_CASE) {
+    fprintf(stderr, "tr16 gemm: no %dx%d tile\n", p.bm, p.bn);
+    abort();
+  }
+#undef PS_TR_CASE
+  // edge strips [0,M) x [N0,N) and [M0,M) x [0,N0): unsplit generic
+  // sub-problems (plain stores over the zeroed C)
+  auto strip = [&](GemmArgs gt) {
+    GemmPlan sp;
+    ps_generic_plan(gemm_shape(gt), &sp, /*may_split=*/false);
+    run_gemm_generic(gt, sp, nullptr, s);
+  };
+  if (N0 != g.N) {
+    GemmArgs gt = g;
+    gt.N = g.N - N0;
+    gt.B = (const void*)((const __bf16*)g.B + N0);
+    gt.C = (void*)((float*)g.C + N0);
+    strip(gt);
+  }
+  if (M0 != g.M) {
+    GemmArgs gt = g;
+    gt.M = g.M - M0; gt.N = N0;
+    gt.A = (const void*)((const __bf16*)g.A + M0);
+    gt.C = (void*)((float*)g.C + (int64_t)M0 * g.ldc);
+    strip(gt);
   }
 }
 
@@ -1235,9 +1213,7 @@ extern "C" {
 
 // tr16 plan first (bf16 in, fp32 out only), else the generic plan
 void ps_gemm_plan(const GemmArgs* g, GemmPlan* plan) {
-  const GemmShape sh = {g->M, g->N, g->K, g->batch, atomic_splitk_ok(*g),
-                        tn_tr_operands_ok(*g), g->gather_b != nullptr,
-                        g->a_klast && g->b_klast};
+  const GemmShape sh = gemm_shape(*g);
   if (!ps_tn_tr_plan(sh, g_tr_tune, plan)) ps_generic_plan(sh, plan);
 }
 
@@ -1249,11 +1225,7 @@ void ps_gemm_set_tr_tune(int bm, int bn, int target) {
 void ps_gemm_run(const GemmArgs* g, const GemmPlan* plan, float* ws,
                  hipStream_t s) {
   if (plan->tr16) return run_gemm_tn_tr(*g, *plan, s);
-  GemmLaunch l = {*g, plan->ws_elems > 0 ? ws : nullptr, plan->splitk};
-  if (l.splitk > 1 && !l.ws) zero_c_for_atomics(*g, s);
-  if (!g->in_bf16) gemm_dispatch<float, float>(l, s);
-  else if (g->out_f32) gemm_dispatch<__bf16, float>(l, s);
-  else gemm_dispatch<__bf16, __bf16>(l, s);
+  run_gemm_generic(*g, *plan, ws, s);
 }
 
 }  // extern "C"

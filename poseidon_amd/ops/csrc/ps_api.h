@@ -14,8 +14,6 @@ struct GemmArgs {
   const float* bias;  // may be null
   int M, N, K;
   int64_t lda, ldb, ldc;
-  int64_t strideA, strideB, strideC;
-  int batch;
   float alpha, beta;
   bool a_klast, b_klast;
   bool in_bf16;   // A/B are bf16 (else fp32)

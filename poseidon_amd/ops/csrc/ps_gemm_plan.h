@@ -1,7 +1,9 @@
-// GEMM plan: path choice, tile and split-K policy for one GEMM, derived ONCE
-// from the problem shape (ps_gemm_plan in gemm.hip fills a GemmShape from
-// its GemmArgs and calls in here). Plain C++ (no torch / HIP includes) so it
-// also compiles into a stand-alone host program (tests/gemm_plan_host.cpp).
+// GEMM plan: every launch decision for one GEMM -- path, tile, split-K, K
+// slice, XCD placement -- derived ONCE from the problem shape (ps_gemm_plan
+// in gemm.hip fills a GemmShape from its GemmArgs and calls in here; the
+// launchers decide nothing). Also the block-index remaps the kernels apply.
+// Plain C++ (no torch / HIP includes) so it also compiles into a stand-alone
+// host program (tests/gemm_plan_host.cpp).
 #pragma once
 #include <cstdint>
 
@@ -17,18 +19,23 @@ struct GemmPlan {
   bool tr16;         // bf16 TN ds_read_b64_tr_b16 path (else generic tiles)
   int splitk;        // 1: no split
   int64_t ws_elems;  // f32 workspace to pass to ps_gemm_run (0: none)
-  int M0, N0, bm, bn, kchunk;  // tr16 only: interior extent, tile, K slice
+  int bm, bn;        // block tile
+  int kchunk;        // K per grid.z slice, a multiple of the staged K tile
+  int M0, N0;        // tr16 only: interior extent (edge strips run generic)
+  int ry, cx;        // generic only: 2D-XCD rectangle in tiles (0: none)
 };
 
 // What planning needs to know of a GEMM (no pointers: the caller folds
 // dtype, layout and alignment eligibility into tr_ok).
 struct GemmShape {
   int M, N, K;
-  int batch;
+  int esize;       // bytes per A/B element
+  int bk;          // K elements per staged LDS tile of that type
   bool atomic_ok;  // atomic split-K may add into C (atomic_splitk_ok)
   bool tr_ok;      // operands can take the tr16 TN kernel at all
   bool gather_b;   // B is gathered (implicit wgrad): no edge strips
   bool nt;         // both operands K-last: the N-fitting tiles exist
+  bool only128;    // A K-major x B K-last (test entry only): 128x128 only
 };
 
 // Manual override of the tr16 tile and split-K block target, 0 = planner's
@@ -39,7 +46,7 @@ struct TrTune {
 };
 
 // ---------------------------------------------------------------------------
-// tr16 tiles: the ONE list both the launcher (gemm.hip PS_TR_LAUNCH) and the
+// tr16 tiles: the ONE list both the launcher (gemm.hip PS_TR_CASE) and the
 // planner draw from. X(bm, bn, wave rows, wave cols); 4 waves per block, the
 // per-wave sub-tile is (bm / wgm) x (bn / wgn).
 // ---------------------------------------------------------------------------
@@ -103,22 +110,52 @@ PS_HD inline bool ps_tr_sub_live(int c0, int i, int cmax) {
 // square-menu tile -- N = 48 / 96 / 192 and their neighbours, where a 128- or
 // 64-column tile idles a quarter of its MFMAs -- not wherever the staging
 // term alone would prefer them (N = 64 stays on 64x64).
+//
+// The ONE list of generic tiles: the candidates below, in this order, and
+// the launcher's dispatch (gemm.hip) are both generated from it.
+// X(bm, bn, wave rows, wave cols, narrow-only). The narrow-only tiles come
+// last: they are judged against the best tile before them.
+#define PS_GEMM_TILE_LIST(X)                                                \
+  X(128, 128, 2, 2, false) X(128, 32, 4, 1, false) X(32, 128, 1, 4, false)  \
+  X(64, 64, 2, 2, false) X(128, 16, 4, 1, false) X(16, 128, 1, 4, false)    \
+  X(128, 96, 2, 2, true) X(128, 48, 4, 1, true)
+
+struct GemmTile {
+  int bm, bn, wgm, wgn;
+  bool narrow_only;
+};
+
+inline const GemmTile* ps_gemm_tiles(int* count) {
+#define PS_GEMM_ROW(BM_, BN_, WGM_, WGN_, NARROW_) \
+  {BM_, BN_, WGM_, WGN_, NARROW_},
+  static const GemmTile tiles[] = {PS_GEMM_TILE_LIST(PS_GEMM_ROW)};
+#undef PS_GEMM_ROW
+  *count = (int)(sizeof(tiles) / sizeof(tiles[0]));
+  return tiles;
+}
+
+inline const GemmTile* ps_gemm_tile(int bm, int bn) {
+  int n;
+  const GemmTile* tiles = ps_gemm_tiles(&n);
+  for (int i = 0; i < n; ++i)
+    if (tiles[i].bm == bm && tiles[i].bn == bn) return &tiles[i];
+  return nullptr;
+}
+
 inline void pick_gemm_tile(int M, int N, int* bm_out, int* bn_out,
-                           bool narrow = false) {
-  const int cand[8][2] = {{128, 128}, {128, 32}, {32, 128}, {64, 64},
-                          {128, 16},  {16, 128}, {128, 96}, {128, 48}};
+                           bool narrow) {
+  int n;
+  const GemmTile* tiles = ps_gemm_tiles(&n);
   const double ALPHA = 400.0;
   double best = -1.0;
   int64_t best_npad = 0;
-  *bm_out = cand[0][0];
-  *bn_out = cand[0][1];
-  for (int i = 0; i < (narrow ? 8 : 6); ++i) {
-    int bm = cand[i][0], bn = cand[i][1];
+  for (int i = 0; i < n; ++i) {
+    const int bm = tiles[i].bm, bn = tiles[i].bn;
     int64_t tm = (M + bm - 1) / bm, tn = (N + bn - 1) / bn;
     double flops = (double)(tm * bm) * (tn * bn) / ALPHA;  // (x K, common)
     double staging = (double)tm * bm * tn + (double)tn * bn * tm;
     double cost = flops + staging;
-    if (i >= 6 && tn * bn >= best_npad) continue;
+    if (tiles[i].narrow_only && (!narrow || tn * bn >= best_npad)) continue;
     if (best < 0 || cost < best) {
       best = cost;
       best_npad = tn * bn;
@@ -187,7 +224,7 @@ inline int64_t ps_tr_tall_splitk(int M0, int N0, int K, int bm, int bn) {
 // kernel), tile (bm, bn) and split-K for the interior.
 inline bool ps_tn_tr_plan(const GemmShape& g, const TrTune& tune,
                           GemmPlan* p) {
-  if (!g.tr_ok || g.batch > 1 || g.K % 64) return false;
+  if (!g.tr_ok || g.K % 64) return false;
   const int M0 = g.M & ~15, N0 = g.N & ~63;
   if (M0 == 0 || N0 == 0) return false;
   if (g.gather_b && (M0 != g.M || N0 != g.N)) return false;
@@ -244,7 +281,7 @@ inline bool ps_tn_tr_plan(const GemmShape& g, const TrTune& tune,
     if (M0 == bm && kchunk > kcap && g.K > kcap) kchunk = kcap;
     sk = (g.K + kchunk - 1) / kchunk;
   }
-  *p = {true, sk, 0, M0, N0, bm, bn, kchunk};
+  *p = {true, sk, 0, bm, bn, kchunk, M0, N0, 0, 0};
   return true;
 }
 
@@ -259,23 +296,58 @@ inline int ps_tr_grid_z(const GemmPlan& p) {
   return skz;
 }
 
-// Generic path: split K when the output tile grid cannot fill 256 CUs but
-// K is deep (conv wgrad: M=Cout, N=Kcol, K=N*OH*OW up to ~800k). 2
-// blocks/CU resident -> ~512 workgroups fill the chip; split K until the
-// grid gets there (wgrad at 512x4608 is 144 tiles = 28% occupancy without).
-inline void ps_generic_plan(const GemmShape& g, GemmPlan* p) {
-  *p = {false, 1, 0, 0, 0, 0, 0, 0};
-  int tbm, tbn;
-  pick_gemm_tile(g.M, g.N, &tbm, &tbn, g.nt);
+// 2D XCD super-tiling for re-read-bound grids (small K, many tiles -- the
+// fc-wgrad class: fc6 dW is 4096x9216x256, each A panel re-read by 72 tile
+// columns and each B panel by 32 rows from HBM/L3). Each XCD owns an ry x cx
+// RECTANGLE of tiles whose A+B panels fit its 4 MiB L2 (3 MiB budget), so
+// panel re-reads inside the rectangle are L2 hits. Unsplit grids of at least
+// 512 full tiles with K <= 1024 only. Picks (ry, cx) with ry | nby,
+// cx | nbx and (nby/ry)*(nbx/cx) == 8, minimizing the L2 working set
+// ry*bm + cx*bn (K common factor); leaves (0, 0) when nothing fits.
+inline void ps_pick_xcd_rect(const GemmShape& g, GemmPlan* p) {
+  p->ry = p->cx = 0;
+  if (p->splitk > 1 || g.K > 1024 || g.M % p->bm || g.N % p->bn) return;
+  const int nby = g.M / p->bm, nbx = g.N / p->bn;
+  if ((int64_t)nby * nbx < 512) return;
+  int64_t best = -1;
+  for (int gy = 1; gy <= 8; gy <<= 1) {
+    const int gx = 8 / gy;
+    if (nby % gy || nbx % gx) continue;
+    const int ry = nby / gy, cx = nbx / gx;
+    const int64_t ws_bytes =
+        ((int64_t)ry * p->bm + (int64_t)cx * p->bn) * g.K * g.esize;
+    if (ws_bytes > (3LL << 20)) continue;  // must fit the 4 MiB L2
+    if (best < 0 || ws_bytes < best) {
+      best = ws_bytes;
+      p->ry = ry;
+      p->cx = cx;
+    }
+  }
+}
+
+// Generic path, every launch decision: tile, split-K, K slice, rectangle.
+// Splits K when the output tile grid cannot fill 256 CUs but K is deep (conv
+// wgrad: M=Cout, N=Kcol, K=N*OH*OW up to ~800k). 2 blocks/CU resident ->
+// ~512 workgroups fill the chip; split K until the grid gets there (wgrad
+// at 512x4608 is 144 tiles = 28% occupancy without). may_split = false
+// plans an unsplit sub-problem (the tr16 edge strips).
+// kchunk rounds the slice up to whole staged tiles, so the last slices of a
+// deep split can be EMPTY (K < splitk * (splitk - 1) * bk, e.g. bf16
+// 128x128x200000 on 512 slices); the kernel adds zeros for those.
+inline void ps_generic_plan(const GemmShape& g, GemmPlan* p,
+                            bool may_split = true) {
+  *p = {false, 1, 0, 0, 0, 0, 0, 0, 0, 0};
+  pick_gemm_tile(g.M, g.N, &p->bm, &p->bn, g.nt);
   const int64_t tiles =
-      (int64_t)((g.M + tbm - 1) / tbm) * ((g.N + tbn - 1) / tbn);
-  if (g.atomic_ok && tiles < 384 && g.K >= 512) {
+      (int64_t)((g.M + p->bm - 1) / p->bm) * ((g.N + p->bn - 1) / p->bn);
+  const bool thin = may_split && tiles < 384;
+  if (thin && g.atomic_ok && g.K >= 512) {
     // atomic split-K: no workspace, so split much deeper (chunk >= 256)
     // -- the un-split grid leaves most of the 256 CUs idle
     const int64_t a = (512 + tiles - 1) / tiles, b = (g.K + 255) / 256;
     int sk = (int)(a < b ? a : b);
     if (sk > 1) p->splitk = sk;
-  } else if (g.batch == 1 && tiles < 384 && g.K >= 4096) {
+  } else if (thin && g.K >= 4096) {
     // workspace split-K + reduce; cap the f32 workspace at 256 MB
     const int64_t a = (512 + tiles - 1) / tiles, b = (g.K + 2047) / 2048;
     int sk = (int)(a < b ? a : b);
@@ -285,4 +357,72 @@ inline void ps_generic_plan(const GemmShape& g, GemmPlan* p) {
       p->ws_elems = ws_elems;
     }
   }
+  // built for 128x128 alone; its split is sized on the menu's tile above,
+  // as it always was
+  if (g.only128) p->bm = p->bn = 128;
+  const int slice = (g.K + p->splitk - 1) / p->splitk;
+  p->kchunk = (slice + g.bk - 1) / g.bk * g.bk;
+  ps_pick_xcd_rect(g, p);
 }
+
+// ---------------------------------------------------------------------------
+// Block-index remaps. The hardware dispatcher places linear block l on XCD
+// l % 8, each with a private 4 MiB L2. Every remap is a PERMUTATION of its
+// launch grid (tests/gemm_plan_host.cpp enumerates them); the kernels call
+// the same functions with gridDim / blockIdx.
+// ---------------------------------------------------------------------------
+struct GemmBlock {
+  int bx, by, bz;
+};
+
+// T1 XCD-aware swizzle: consecutive tiles share A/B panels, so give each XCD
+// a CONTIGUOUS run of tiles instead of a round-robin comb. Bijective only
+// when the flattened grid is a multiple of 8 -- identity otherwise. z (the
+// split-K slice) folds into the flatten so the remap stays a permutation of
+// the whole grid.
+PS_HD inline GemmBlock ps_remap_linear(int nbx, int nby, int nbz, int bx,
+                                       int by, int bz) {
+  const int64_t nwg = (int64_t)nbx * nby * nbz;
+  if ((nwg & 7) == 0 && nwg > 8) {
+    int64_t id = ((int64_t)bz * nby + by) * nbx + bx;
+    const int64_t cpx = nwg >> 3;
+    id = (id & 7) * cpx + (id >> 3);
+    bx = (int)(id % nbx);
+    by = (int)((id / nbx) % nby);
+    bz = (int)(id / ((int64_t)nbx * nby));
+  }
+  return {bx, by, bz};
+}
+
+// The planned rectangle (ps_pick_xcd_rect): XCD k owns rectangle k, and its
+// j-th block takes the rectangle's j-th tile, row-major. Needs nby % ry == 0,
+// nbx % cx == 0, (nby/ry)*(nbx/cx) == 8 and grid.z == 1.
+PS_HD inline GemmBlock ps_remap_rect(int nbx, int ry, int cx, int bx,
+                                     int by) {
+  const int regs_x = nbx / cx;
+  const int64_t l = (int64_t)by * nbx + bx;
+  const int k = (int)(l & 7);
+  const int64_t j = l >> 3;
+  return {(k % regs_x) * cx + (int)(j % cx), (k / regs_x) * ry + (int)(j / cx),
+          0};
+}
+
+// tr16 L2-reuse placement: all nbx tiles of one (by, bz) group -- they
+// stage the SAME A k-slice (bm x kchunk, a few MB) -- land on ONE XCD so
+// the re-reads hit that XCD's 4 MiB L2 (34.5 TB/s aggregate) instead of
+// HBM: group g goes to XCD g % 8 and its tiles get consecutive slots there.
+// Split launches whose nby * nbz is a multiple of 8 only (ps_tr_grid_z pads
+// grid.z until it is; padded bz blocks have no K slice and exit); every
+// other grid takes the linear swizzle.
+PS_HD inline GemmBlock ps_remap_tr(bool splitk, int nbx, int nby, int nbz,
+                                   int bx, int by, int bz) {
+  const int64_t G = (int64_t)nby * nbz;  // (by, bz) groups
+  if (!(splitk && (G & 7) == 0 && G >= 8))
+    return ps_remap_linear(nbx, nby, nbz, bx, by, bz);
+  const int64_t l = ((int64_t)bz * nby + by) * nbx + bx;
+  const int xcd = (int)(l & 7);
+  const int64_t j = l >> 3;
+  const int g2 = (int)((j / nbx) * 8 + xcd);
+  return {(int)(j % nbx), g2 % nby, g2 / nby};
+}
+

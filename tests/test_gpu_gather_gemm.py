@@ -18,7 +18,13 @@ The N-fitting tiles 128x96 and 128x48 (plain NT ext.gemm, ragged M): max abs
 error against an fp64 reference from bf16-quantised inputs, held to 4x the
 error of the parent's 128x128 / 64x64 tiles on the same shapes
 (PARENT_TILE_ERR). tests/gather_walk_host.cpp checks that the planner gives
-these shapes those tiles."""
+these shapes those tiles.
+
+Remapped grids (plain NT ext.gemm, bf16 and one fp32): the planned 2D-XCD
+rectangle and the linear XCD swizzle on more than 8 blocks, by the same
+measure and rule; their PARENT_TILE_ERR entries are the commit before the
+remaps moved into ps_gemm_plan.h (which gave bit-equal results).
+tests/gemm_plan_host.cpp pins the plans of these shapes."""
 
 import pytest
 import torch
@@ -159,20 +165,33 @@ def test_dgrad_as_forward(data, name):
 # (M, N, K) -> max abs error of the parent commit (f32 output: accumulation
 # order only). K = 333 has rows that are not 16 B multiples (register
 # staging), K = 320 is all direct-to-LDS tiles, K = 200 leaves an 8-wide tail.
+N_FITTING = [(300, 96, 320), (300, 192, 333), (260, 48, 200)]
+# Grids whose block -> tile remap (ps_gemm_plan.h) is more than the identity:
+# the planned 2D-XCD rectangle, and the linear swizzle on more than 8 blocks.
+# A fourth element "f32" runs the shape in fp32 (else bf16 in, f32 out).
+XCD_GRIDS = [(2048, 4096, 64), (2048, 4096, 64, "f32"), (64, 32768, 64),
+             (512, 512, 96)]
 PARENT_TILE_ERR = {
     (300, 96, 320): 1.322e-06,    # 128x96
     (300, 192, 333): 1.561e-06,   # 128x96, two column tiles
     (260, 48, 200): 1.356e-06,    # 128x48
+    (2048, 4096, 64): 5.933e-07,         # 128x128, rectangle 8x8
+    (2048, 4096, 64, "f32"): 1.547e-06,  # the same plan on the fp32 MFMA
+    (64, 32768, 64): 5.933e-07,          # 64x64, rectangle 1x64
+    # 16 blocks, linear swizzle; one glds tile, then a 32-wide K tail
+    (512, 512, 96): 5.355e-07,
 }
 
 
 def make_tile_data():
     out = {}
-    for (M, N, K) in PARENT_TILE_ERR:
-        a = rnd(M, K, seed=31) * 0.3
-        b = rnd(N, K, seed=32) * 0.3
-        ref = a.to(torch.bfloat16).double() @ b.to(torch.bfloat16).double().t()
-        out[(M, N, K)] = (a, b, ref)
+    for shape in PARENT_TILE_ERR:
+        M, N, K = shape[:3]
+        dt = torch.float32 if shape[3:] == ("f32",) else torch.bfloat16
+        a = (rnd(M, K, seed=31) * 0.3).to(dt)
+        b = (rnd(N, K, seed=32) * 0.3).to(dt)
+        ref = a.double() @ b.double().t()
+        out[shape] = (a, b, ref)
     return out
 
 
@@ -183,21 +202,32 @@ def tile_data():
 
 def tile_error(shape, t):
     from poseidon_amd.ops._backend import load
-    M, N, K = shape
-    a, b, ref = t
-    out = load().gemm(a.to(DEV, torch.bfloat16), b.to(DEV, torch.bfloat16),
-                      M, N, K, True, True)
+    M, N, K = shape[:3]
+    a, b, ref = t  # already at the case's dtype
+    out = load().gemm(a.to(DEV), b.to(DEV), M, N, K, True, True)
     torch.cuda.synchronize()
     assert out.dtype == torch.float32 and tuple(out.shape) == (M, N)
     return (out.cpu().double() - ref).abs().max().item()
 
 
-@pytest.mark.parametrize("shape", list(PARENT_TILE_ERR),
-                         ids=lambda s: "x".join(map(str, s)))
-def test_n_fitting_tiles(tile_data, shape):
+def _check_tile(tile_data, shape):
     err = tile_error(shape, tile_data[shape])
     bound = 4.0 * PARENT_TILE_ERR[shape]
     print(f"gemm {shape}: max abs err {err:.3e} (bound {bound:.3e}, "
           f"parent {PARENT_TILE_ERR[shape]:.3e})")
     assert err <= bound, \
         f"gemm {shape}: max abs {err:.3e} > 4 x parent {PARENT_TILE_ERR[shape]:.3e}"
+
+
+def _shape_id(s):
+    return "x".join(map(str, s))
+
+
+@pytest.mark.parametrize("shape", N_FITTING, ids=_shape_id)
+def test_n_fitting_tiles(tile_data, shape):
+    _check_tile(tile_data, shape)
+
+
+@pytest.mark.parametrize("shape", XCD_GRIDS, ids=_shape_id)
+def test_remapped_grids(tile_data, shape):
+    _check_tile(tile_data, shape)
