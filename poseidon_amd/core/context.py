@@ -33,6 +33,12 @@ class _Context:
     device_transform: bool = field(
         default_factory=lambda: os.environ.get("PS_DEVICE_TRANSFORM", "0")
         not in ("", "0"))
+    # bit-reproducible float reductions on the GPU (ops.set_deterministic);
+    # off by default, PS_DETERMINISTIC=1 turns it on at import. One process
+    # on one GPU: multi-rank runs are outside the guarantee.
+    deterministic: bool = field(
+        default_factory=lambda: os.environ.get("PS_DETERMINISTIC", "0")
+        not in ("", "0"))
     phase_stack: list = field(default_factory=list)
 
     @property
@@ -55,7 +61,8 @@ def ctx() -> _Context:
 def init(device: Optional[str] = None, rank: Optional[int] = None,
          world_size: Optional[int] = None, seed: Optional[int] = None,
          compute_dtype: Optional[torch.dtype] = None,
-         device_transform: Optional[bool] = None) -> _Context:
+         device_transform: Optional[bool] = None,
+         deterministic: Optional[bool] = None) -> _Context:
     """(Re)configure the global context. Reads torchrun env vars when args
     are omitted."""
     if rank is None:
@@ -81,4 +88,8 @@ def init(device: Optional[str] = None, rank: Optional[int] = None,
         _ctx.compute_dtype = compute_dtype
     if device_transform is not None:
         _ctx.device_transform = bool(device_transform)
+    if deterministic is not None:
+        from ..ops import functional as ops
+        ops.set_deterministic(bool(deterministic))
+        _ctx.deterministic = bool(deterministic)
     return _ctx

@@ -583,6 +583,8 @@ class Net:
             # sight of a new key -- the set settles by warmup iteration 3
             key = [(dy.data_ptr(), db.data_ptr(), tuple(dy.shape))
                    for _, (dy, db) in pend]
+            # deterministic mode sizes the table's scratch at prepare time
+            key.append(ops.conv_policy_epoch())
             if self._colsum_mt is None or self._colsum_mt[1] != key:
                 self._colsum_mt = (ops.colsum_mt_prepare(
                     [dy for _, (dy, db) in pend],

@@ -119,8 +119,13 @@ class ConvolutionLayer(Layer):
                    and dy.is_contiguous(memory_format=torch.channels_last)
                    else None)
             fused_db = self.bias_grad_by_consumer
+            # Deterministic mode never defers: whether a dy pointer repeats
+            # depends on the allocator's state, and the batched and the
+            # in-call column sums add in different (each fixed) orders, so
+            # the choice between them must not hang on an address.
             defer_db = (defer and self.bias_term and ptr is not None
-                        and ptr == self._last_dy_ptr and not fused_db)
+                        and ptr == self._last_dy_ptr and not fused_db
+                        and not ops.deterministic())
             self._last_dy_ptr = ptr
             db = self.blobs[1].diff.view(-1) if self.bias_term else None
             cache = self._colT[i]

@@ -135,6 +135,25 @@ void set_packed_conv(bool on) { g_packed_conv.store(on); }
 void set_implicit_threshold(int64_t bytes) { g_implicit_thresh.store(bytes); }
 void set_dgrad_fwd_threshold(int64_t bytes) { g_dgrad_fwd_thresh.store(bytes); }
 
+// Deterministic mode (ps_api.h): bit-reproducible float reductions. The
+// launchers choose the ordered kernels by the flag; the bindings allocate the
+// scratch those need (torch allocations, so they are graph-capture safe) and
+// raise where no ordered form exists.
+bool deterministic() { return ps_deterministic() != 0; }
+void set_deterministic(bool on) { ps_set_deterministic(on ? 1 : 0); }
+int64_t float_atomic_launches(bool reset) {
+  return ps_float_atomic_launches(reset ? 1 : 0);
+}
+
+// out[c] += column sums of d[R][C] (out: f32 [C] on d's device)
+void colsum_into(const Tensor& d, float* out, int64_t R, int C) {
+  Tensor scratch;  // deterministic mode: [blocks][C] partials
+  const int64_t n = ps_colsum_scratch_elems(R, C, is_bf16(d) ? 1 : 0);
+  if (n > 0) scratch = at::empty({n}, d.options().dtype(at::kFloat));
+  PS_CALL(colsum, is_bf16(d), P(d), out, R, C,
+          n > 0 ? scratch.data_ptr<float>() : nullptr, stream());
+}
+
 // 64B zero page for implicit-GEMM padding loads (per device, persistent)
 const void* zero_page(const Tensor& like) {
   static Tensor z;
@@ -172,6 +191,9 @@ void run_gemm(const Tensor& A, const Tensor& B, Tensor& C,
   g.c_prezeroed = c_prezeroed;
   GemmPlan plan;
   ps_gemm_plan(&g, &plan);
+  TORCH_CHECK(!deterministic() || plan.splitk == 1 || plan.ws_elems > 0,
+              "gemm: deterministic mode has no ordered form of this split-K "
+              "plan (", M, "x", N, "x", K, ")");
   Tensor ws;  // keep alive until launch returns
   if (plan.ws_elems > 0)
     ws = at::empty({plan.ws_elems}, C.options().dtype(at::kFloat));
@@ -191,6 +213,36 @@ Tensor gemm(const Tensor& A, const Tensor& B, int M, int N, int K,
   run_gemm(Ac, Bc, C, nullptr, M, N, K, lda, ldb, N, 0, 0, 0,
            a_klast, b_klast, 1.0f, 0.0f);
   return C;
+}
+
+// The plan gemm() above would run for this shape right now (tests, tuning):
+// path, tile, split-K depth, K slice and workspace size.
+py::dict gemm_plan(int M, int N, int K, bool a_klast, bool b_klast,
+                   bool bf16) {
+  GemmArgs g{};
+  // planning reads the operands' alignment only; gemm() passes fresh
+  // allocations, which are 256 B aligned
+  g.A = g.B = reinterpret_cast<const void*>(uintptr_t{256});
+  g.C = reinterpret_cast<void*>(uintptr_t{256});
+  g.M = M; g.N = N; g.K = K;
+  g.lda = a_klast ? K : M;
+  g.ldb = b_klast ? K : N;
+  g.ldc = N;
+  g.alpha = 1.0f;
+  g.a_klast = a_klast; g.b_klast = b_klast;
+  g.in_bf16 = bf16;
+  g.out_f32 = true;
+  GemmPlan p;
+  ps_gemm_plan(&g, &p);
+  py::dict d;
+  d["tr16"] = p.tr16;
+  d["splitk"] = p.splitk;
+  d["ws_elems"] = p.ws_elems;
+  d["bm"] = p.bm;
+  d["bn"] = p.bn;
+  d["kchunk"] = p.kchunk;
+  d["grid_z"] = p.tr16 ? ps_tr_grid_z(p) : p.splitk;
+  return d;
 }
 
 // ---------------------------------------------------------------------------
@@ -260,7 +312,7 @@ std::vector<c10::optional<Tensor>> linear_backward(
   }
   if (has_bias) {
     Tensor t = at::zeros({N}, x.options().dtype(at::kFloat));
-    PS_CALL(colsum, is_bf16(dyc), P(dyc), t.data_ptr<float>(), M, N, stream());
+    colsum_into(dyc, t.data_ptr<float>(), M, N);
     db = t;
   }
   return {dx, dw, db};
@@ -579,8 +631,7 @@ Tensor conv2d_backward_weight_acc(const Tensor& x, const Tensor& colT,
                             Co, p.Cg, p.g.kh, p.g.kw, /*ld=*/Kgw,
                             /*beta=*/1.0f, p.kw_ld, p.c_ld, stream());
   if (db_out.has_value() && !skip_db)
-    PS_CALL(colsum, is_bf16(dy_cl), P(dy_cl), db_out->data_ptr<float>(), p.NP,
-            Co, stream());
+    colsum_into(dy_cl, db_out->data_ptr<float>(), p.NP, Co);
   return dwk;
 }
 
@@ -890,6 +941,14 @@ float* tail_db(const c10::optional<Tensor>& db, int C) {
               "bias gradient: contiguous f32 device tensor of C elements");
   return db->data_ptr<float>();
 }
+// Deterministic mode: the tail kernels run WITHOUT their bias flush (LDS and
+// global float atomics) -- dx keeps the mask fusion -- and the bias gradient
+// is the ordered column sum of the stored dx, which is the very set of
+// values the flush would have added.
+float* tail_kernel_db(float* db) { return deterministic() ? nullptr : db; }
+void tail_db_ordered(const Tensor& dx, float* db, int C) {
+  if (db && deterministic()) colsum_into(dx, db, dx.numel() / C, C);
+}
 
 // LRN backward on the vec8 path. pool_mask given: dy is the top diff of the
 // max pool that consumes this LRN's output (mask and geometry are that
@@ -927,9 +986,12 @@ Tensor lrn_backward_tail(const Tensor& x, const Tensor& y, const Tensor& dy,
   } else {
     TORCH_CHECK(dy.sizes() == x.sizes());
   }
+  float* dbp = tail_db(db, C);
   PS_CALL(lrn_bwd_v8_tail, is_bf16(x), P(x_cl), P(y_cl), P(dy_cl), mask, &g,
-          P(dx), tail_db(db, C), relu ? 1 : 0, rows, C, size, (float)alpha,
-          (float)beta, tail_blocks(lrn_tail_blocks(C)), stream());
+          P(dx), tail_kernel_db(dbp), relu ? 1 : 0, rows, C, size,
+          (float)alpha, (float)beta, tail_blocks(lrn_tail_blocks(C)),
+          stream());
+  tail_db_ordered(dx, dbp, C);
   return dx;
 }
 
@@ -952,9 +1014,11 @@ Tensor pool_max_backward_tail(const Tensor& dy, const Tensor& mask,
               g.Wo == pool_out(g.W, kw, pw, sw) && g.C * 4 <= 64 * 1024,
               "pool tail: operands do not match the geometry");
   Tensor dx = reuse_or_empty_cl(dx_out, x.sizes(), dy);
+  float* dbp = tail_db(db, g.C);
   PS_CALL(maxpool_bwd_tail, is_bf16(dy), P(dy_cl), mask_cl.data_ptr<uint8_t>(),
-          P(x_cl), P(dx), tail_db(db, g.C), &g, tail_blocks(pool_tail_blocks(g.C)),
-          stream());
+          P(x_cl), P(dx), tail_kernel_db(dbp), &g,
+          tail_blocks(pool_tail_blocks(g.C)), stream());
+  tail_db_ordered(dx, dbp, g.C);
   return dx;
 }
 
@@ -970,8 +1034,17 @@ Tensor relu_backward_bias(const Tensor& x, Tensor dy, Tensor db) {
   TORCH_CHECK(x.sizes() == dy.sizes() && x.scalar_type() == dy.scalar_type() &&
               C % (is_bf16(x) ? 8 : 4) == 0 && C * 4 <= 64 * 1024,
               "relu_backward_bias: mismatched operands or unaligned channels");
-  PS_CALL(relu_bwd_bias, is_bf16(x), P(xc), P(dyc), P(dyc), tail_db(db, C),
-          rows, C, tail_blocks(relu_tail_blocks(C)), stream());
+  float* dbp = tail_db(db, C);
+  if (deterministic()) {
+    // the plain slope-0 ReLU backward stores the same dx (g * 0 keeps its
+    // sign bit there too), then the ordered column sum of it
+    PS_CALL(relu_bwd, is_bf16(x), P(xc), P(dyc), P(dyc), rows * C, 0.0f,
+            stream());
+    tail_db_ordered(dyc, dbp, C);
+    return dy;
+  }
+  PS_CALL(relu_bwd_bias, is_bf16(x), P(xc), P(dyc), P(dyc), dbp, rows, C,
+          tail_blocks(relu_tail_blocks(C)), stream());
   return dy;
 }
 
@@ -1016,8 +1089,13 @@ std::vector<Tensor> softmax_loss_forward(const Tensor& logits,
   int C = xc.size(1);
   Tensor prob = at::empty_like(xc);
   Tensor loss = at::zeros({}, xc.options().dtype(at::kFloat));
+  Tensor row_loss;  // deterministic mode: per-row terms, summed in order
+  if (deterministic())
+    row_loss = at::empty({rows}, loss.options());
   PS_CALL(softmax_loss_fwd, is_bf16(xc), P(xc), lc.data_ptr<float>(), P(prob),
-          loss.data_ptr<float>(), rows, C, stream());
+          loss.data_ptr<float>(),
+          row_loss.defined() ? row_loss.data_ptr<float>() : nullptr, rows, C,
+          stream());
   loss.div_((double)rows);
   return {loss, prob};
 }
@@ -1316,13 +1394,27 @@ std::vector<Tensor> colsum_mt_prepare(std::vector<Tensor> dys,
     return std::pair<int64_t, int64_t>(d.R, d.rows_per);
   });
   mt.push_back(at::scalar_tensor((int64_t)max_c));
+  // [4] tensors in the table, [5] deterministic mode's [nchunks][max_c]
+  // partials: sized here, once, so a captured graph keeps a stable pointer
+  // (empty when the table is prepared with the mode off)
+  const int64_t nchunks = mt[1].numel() * mt[1].element_size() /
+                          (int64_t)sizeof(ps::ColsumChunk);
+  mt.push_back(at::scalar_tensor((int64_t)dys.size()));
+  mt.push_back(at::empty({deterministic() ? nchunks * max_c : 0},
+                         dys[0].options().dtype(at::kFloat)));
   return mt;
 }
 
 void colsum_mt_run(const Tensor& desc_dev, const Tensor& chunk_dev,
-                   int64_t nchunks, bool bf16, int64_t max_c) {
+                   int64_t nchunks, bool bf16, int64_t max_c,
+                   int64_t ntensors, const Tensor& scratch) {
+  TORCH_CHECK(!deterministic() || scratch.numel() >= nchunks * max_c,
+              "colsum_mt: table was prepared with deterministic mode off; "
+              "prepare it again");
   ps_colsum_mt(desc_dev.data_ptr(), chunk_dev.data_ptr(), (int)nchunks,
-               bf16 ? 1 : 0, (int)max_c, stream());
+               bf16 ? 1 : 0, (int)max_c, (int)ntensors,
+               deterministic() ? scratch.data_ptr<float>() : nullptr,
+               stream());
 }
 
 // one table for every deferred conv-wgrad unpack (dwk khwc -> dw NCHW,
@@ -1410,7 +1502,7 @@ void colsum_acc(const Tensor& dy, Tensor db) {
   int64_t R;
   int C;
   Tensor d = as_rows(dy, &R, &C);
-  PS_CALL(colsum, is_bf16(d), P(d), db.data_ptr<float>(), R, C, stream());
+  colsum_into(d, db.data_ptr<float>(), R, C);
 }
 
 // ---------------------------------------------------------------------------
@@ -1473,6 +1565,7 @@ void data_transform(const Tensor& raw, const Tensor& params,
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("data_transform", &data_transform);
   m.def("gemm", &gemm);
+  m.def("gemm_plan", &gemm_plan);
   m.def("linear_forward", &linear_forward);
   m.def("linear_backward", &linear_backward);
   m.def("gemm_at_b", &gemm_at_b);
@@ -1481,6 +1574,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("conv2d_backward_input", &conv2d_backward_input);
   m.def("conv2d_backward_weight_acc", &conv2d_backward_weight_acc);
   m.def("set_implicit_gemm", &set_implicit_gemm);
+  m.def("set_deterministic", &set_deterministic);
+  m.def("deterministic", &deterministic);
+  m.def("float_atomic_launches", &float_atomic_launches);
   // tests / tuning: force the tr16 TN tile and its split-K block target
   // (all 0 = the planner's choice)
   m.def("set_tr16_tune", &ps_gemm_set_tr_tune);

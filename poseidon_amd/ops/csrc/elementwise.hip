@@ -234,7 +234,11 @@ __global__ void contrastive_fwd_k(const float* dist_sq, const float* sim,
 // consecutive columns (coalesced) with 4 row-phases, LDS-reduce the 4
 // partials per column, then one atomicAdd per (block, column)
 // (guide §6 Guideline 12: partial-reduce first, few atomics).
-template <typename T>
+// DET (deterministic mode): a multi-block launch gets the [blocks][C] scratch
+// as `out` and block b stores its partials into row b; colsum_fin_k then adds
+// the rows in block order into the real out. Inside a block the four row
+// groups were always summed in a fixed order.
+template <typename T, bool DET = false>
 __global__ void colsum_k(const T* __restrict__ in, float* __restrict__ out,
                          int64_t R, int C) {
   typedef T vec2 __attribute__((ext_vector_type(2)));
@@ -274,11 +278,38 @@ __global__ void colsum_k(const T* __restrict__ in, float* __restrict__ out,
         float v = part[0][idx] + part[1][idx] + part[2][idx] + part[3][idx];
         if (gridDim.x == 1)
           out[c] += v;
+        else if (DET)
+          out[(int64_t)blockIdx.x * C + c] = v;
         else
           atomicAdd(&out[c], v);
       }
     }
     __syncthreads();
+  }
+}
+
+// Second pass of the deterministic column sums over the [blocks][C] scratch
+// (ld floats per row). A block of 256 threads owns 16 columns x 16 phases:
+// phase p adds rows p, p + 16, ... in ascending order (64 B segments per
+// row), then one thread per column adds the 16 phase sums in ascending
+// order into out (+=). The order depends on blocks alone. One thread per
+// column walking all rows was a chain of up to 1024 dependent loads: 122 us
+// per launch on AlexNet's bias gradients.
+__global__ void colsum_fin_k(const float* __restrict__ scratch,
+                             float* __restrict__ out, int blocks, int C,
+                             int ld) {
+  __shared__ float part[16][17];
+  const int cl = threadIdx.x & 15, ph = threadIdx.x >> 4;
+  const int c = blockIdx.x * 16 + cl;
+  float v = 0.f;
+  if (c < C)
+    for (int b = ph; b < blocks; b += 16) v += scratch[(int64_t)b * ld + c];
+  part[ph][cl] = v;
+  __syncthreads();
+  if (ph == 0 && c < C) {
+    float s = 0.f;
+    for (int p = 0; p < 16; ++p) s += part[p][cl];
+    out[c] += s;
   }
 }
 
@@ -290,13 +321,21 @@ __global__ void colsum_k(const T* __restrict__ in, float* __restrict__ out,
 // and touches LDS only once at flush (a per-load LDS-atomic variant
 // serialized on slot contention and measured slower than the banded
 // kernel). PH > 4 falls back to the banded kernel.
-template <typename T, int VEC, int PH>
+// DET (deterministic mode): part is [256][PH * VEC] floats and out the
+// [blocks][C] scratch. Every thread stores its register partials to its own
+// LDS row; thread t's phase q holds column chunk (i0 + q * rot / VEC) mod
+// (C / VEC), i0 its first vector index, so one thread per column adds, phase
+// by phase, the threads that hold it in ascending thread order and stores the
+// block's sum into scratch row blockIdx.x (colsum_fin_k adds the rows).
+template <typename T, int VEC, int PH, bool DET = false>
 __global__ void colsum_flat_k(const T* __restrict__ in,
                               float* __restrict__ out, int64_t R, int C,
                               int rot) {
-  extern __shared__ float part[];  // C floats
-  for (int c = threadIdx.x; c < C; c += blockDim.x) part[c] = 0.f;
-  __syncthreads();
+  extern __shared__ float part[];  // C floats (DET: 256 * PH * VEC)
+  if (!DET) {
+    for (int c = threadIdx.x; c < C; c += blockDim.x) part[c] = 0.f;
+    __syncthreads();
+  }
   typedef T vecT __attribute__((ext_vector_type(VEC)));
   const int64_t nvec = R * C / VEC;
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
@@ -318,6 +357,29 @@ __global__ void colsum_flat_k(const T* __restrict__ in,
 #pragma unroll
     for (int j = 0; j < VEC; ++j) acc[p][j] += to_f32(v[j]);
     if (PH > 1 && ++p == PH) p = 0;
+  }
+  if (DET) {
+#pragma unroll
+    for (int q = 0; q < PH; ++q)
+#pragma unroll
+      for (int j = 0; j < VEC; ++j)
+        part[threadIdx.x * (PH * VEC) + q * VEC + j] = acc[q][j];
+    __syncthreads();
+    const int CV = C / VEC, rotv = rot / VEC;
+    const int b0 = (int)(((int64_t)blockIdx.x * blockDim.x) % CV);
+    for (int c = threadIdx.x; c < C; c += blockDim.x) {
+      const int k = c / VEC, j = c % VEC;
+      float v = 0.f;
+      for (int q = 0; q < PH; ++q) {
+        // threads t with (b0 + t + q * rotv) mod CV == k
+        int t0 = (int)((k - b0 - (int64_t)q * rotv) % CV);
+        if (t0 < 0) t0 += CV;
+        for (int t = t0; t < (int)blockDim.x; t += CV)
+          v += part[t * (PH * VEC) + q * VEC + j];
+      }
+      out[(int64_t)blockIdx.x * C + c] = v;
+    }
+    return;
   }
 #pragma unroll
   for (int q = 0; q < PH; ++q) {
@@ -407,6 +469,88 @@ __global__ void colsum_mt_k(const ColsumDesc* __restrict__ descs,
   __syncthreads();
   for (int c = threadIdx.x; c < C; c += 256)
     atomicAdd(&d.db[c], part[c]);
+}
+
+// Deterministic colsum_mt_k: the same slabs, chunks and row phases, but every
+// thread's register partials go to LDS with plain stores ([phase][C], at most
+// 256 * VEC floats), one thread per column adds the phases in ascending
+// order, and the block stores its C sums into row blockIdx.x of the
+// [nchunks][max_c] scratch. C > 256 * VEC: a column chunk has one owner
+// thread, which stores straight to the scratch.
+template <typename T>
+__global__ void colsum_mt_det_k(const ColsumDesc* __restrict__ descs,
+                                const ColsumChunk* __restrict__ chunks,
+                                float* __restrict__ scratch, int max_c) {
+  constexpr int VEC = 16 / (int)sizeof(T);
+  typedef T vecT __attribute__((ext_vector_type(VEC)));
+  __shared__ float part[256 * VEC];
+  const ColsumChunk ck = chunks[blockIdx.x];
+  const ColsumDesc d = descs[ck.t];
+  const T* in = (const T*)d.dy;
+  const int C = d.C;
+  const int CV = C / VEC;
+  const int nph = 256 / CV;
+  const int t = (int)threadIdx.x;
+  const int64_t r1 = min(d.R, ck.off + d.rows_per);
+  float* row = scratch + (int64_t)blockIdx.x * max_c;
+  if (nph == 0) {
+    for (int cv = t; cv < CV; cv += 256) {
+      float acc[VEC];
+#pragma unroll
+      for (int j = 0; j < VEC; ++j) acc[j] = 0.f;
+      for (int64_t r = ck.off; r < r1; ++r) {
+        vecT v = *(((const vecT*)&in[r * C]) + cv);
+#pragma unroll
+        for (int j = 0; j < VEC; ++j) acc[j] += to_f32(v[j]);
+      }
+#pragma unroll
+      for (int j = 0; j < VEC; ++j) row[cv * VEC + j] = acc[j];
+    }
+    return;
+  }
+  if (t < nph * CV) {
+    const int cv = t % CV;
+    const int ph = t / CV;
+    float acc[VEC];
+#pragma unroll
+    for (int j = 0; j < VEC; ++j) acc[j] = 0.f;
+    for (int64_t r = ck.off + ph; r < r1; r += nph) {
+      vecT v = *(((const vecT*)&in[r * C]) + cv);
+#pragma unroll
+      for (int j = 0; j < VEC; ++j) acc[j] += to_f32(v[j]);
+    }
+#pragma unroll
+    for (int j = 0; j < VEC; ++j) part[ph * C + cv * VEC + j] = acc[j];
+  }
+  __syncthreads();
+  for (int c = t; c < C; c += 256) {
+    float v = 0.f;
+    for (int ph = 0; ph < nph; ++ph) v += part[ph * C + c];
+    row[c] = v;
+  }
+}
+
+// One block per tensor: db[c] += its chunks' scratch rows in ascending chunk
+// order. The table lists a tensor's chunks contiguously, tensors ascending.
+__global__ void colsum_mt_fin_k(const ColsumDesc* __restrict__ descs,
+                                const ColsumChunk* __restrict__ chunks,
+                                int nchunks,
+                                const float* __restrict__ scratch,
+                                int max_c) {
+  const int t = blockIdx.x;
+  const ColsumDesc d = descs[t];
+  int lo = 0, hi = nchunks;  // first chunk of tensor t
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (chunks[mid].t < t) lo = mid + 1;
+    else hi = mid;
+  }
+  for (int c = threadIdx.x; c < d.C; c += blockDim.x) {
+    float v = 0.f;
+    for (int b = lo; b < nchunks && chunks[b].t == t; ++b)
+      v += scratch[(int64_t)b * max_c + c];
+    d.db[c] += v;
+  }
 }
 
 extern "C" {
@@ -499,6 +643,7 @@ void ps_relu_bwd_bias_f32(const float* x, const float* dy, float* dx,
                           float* db, int64_t rows, int C, int max_blocks,
                           hipStream_t s) {
   const int64_t nvec = rows * C / 4;
+  bias_flush_launch(db, "relu_bwd_bias");
   relu_bwd_bias_k<float, 4><<<dim3(bias_flat_blocks(nvec, C / 4, max_blocks)),
                               256, C * 4, s>>>(x, dy, dx, db, nvec, C);
 }
@@ -506,6 +651,7 @@ void ps_relu_bwd_bias_bf16(const void* x, const void* dy, void* dx, float* db,
                            int64_t rows, int C, int max_blocks,
                            hipStream_t s) {
   const int64_t nvec = rows * C / 8;
+  bias_flush_launch(db, "relu_bwd_bias");
   relu_bwd_bias_k<__bf16, 8><<<dim3(bias_flat_blocks(nvec, C / 8, max_blocks)),
                                256, C * 4, s>>>(
       (const __bf16*)x, (const __bf16*)dy, (__bf16*)dx, db, nvec, C);
@@ -546,6 +692,8 @@ void ps_dropout_bwd_bf16(const void* dy, const uint8_t* mask, void* dx,
                1.0f / (1.0f - ratio));
 }
 
+}  // extern "C"
+
 static inline dim3 colsum_grid(int64_t R, int C) {
   // row slabs: fill the chip but keep >= ~64 rows per block
   int64_t blocks = R / 64;
@@ -558,6 +706,7 @@ static inline dim3 colsum_grid(int64_t R, int C) {
     dim3 grid_ = colsum_flat_grid(R * C / VEC);                               \
     int rot_ = (int)(((int64_t)grid_.x * 256 * VEC) % C);                     \
     int ph_ = rot_ ? C / colsum_gcd(rot_, C) : 1;                             \
+    if (ph_ <= 4) ps_count_float_atomic();                                    \
     if (ph_ == 1)                                                             \
       colsum_flat_k<T, VEC, 1><<<grid_, 256, C * 4, s>>>(inexpr, out, R, C,   \
                                                          rot_);              \
@@ -571,28 +720,132 @@ static inline dim3 colsum_grid(int64_t R, int C) {
       colsum_flat_k<T, VEC, 4><<<grid_, 256, C * 4, s>>>(inexpr, out, R, C,   \
                                                          rot_);              \
     else                                                                      \
-      colsum_k<T><<<colsum_grid(R, C), 256, 0, s>>>(inexpr, out, R, C);       \
+      colsum_banded<T>(inexpr, out, R, C, s);                                 \
   } while (0)
 
-void ps_colsum_f32(const float* in, float* out, int64_t R, int C, hipStream_t s) {
+// the banded kernel adds atomically only across blocks
+template <typename T>
+static void colsum_banded(const T* in, float* out, int64_t R, int C,
+                          hipStream_t s) {
+  const dim3 grid = colsum_grid(R, C);
+  if (grid.x > 1) ps_count_float_atomic();
+  colsum_k<T><<<grid, 256, 0, s>>>(in, out, R, C);
+}
+
+// Deterministic mode takes the default launcher's route (flat for the same
+// shapes, banded for the rest) through the kernels' DET forms: every block
+// stores its C sums into its row of the [blocks][C] scratch and colsum_fin_k
+// adds the rows in order. A banded launch of one block adds nothing
+// atomically and needs no scratch.
+struct ColsumDetRoute {
+  bool flat;
+  dim3 grid;
+  int rot, ph;
+};
+static ColsumDetRoute colsum_det_route(int64_t R, int C, int vec) {
+  ColsumDetRoute r{false, colsum_grid(R, C), 0, 0};
+  if (C % vec == 0 && C <= 8192 &&
+      (R * C >= (8 << 20) || (R < 1024 && C >= 512))) {
+    const dim3 g = colsum_flat_grid(R * C / vec);
+    const int rot = (int)(((int64_t)g.x * 256 * vec) % C);
+    const int ph = rot ? C / colsum_gcd(rot, C) : 1;
+    if (ph <= 4) r = {true, g, rot, ph};
+  }
+  return r;
+}
+
+template <typename T, int VEC>
+static void colsum_det(const T* in, float* out, int64_t R, int C,
+                       float* scratch, hipStream_t s) {
+  const ColsumDetRoute r = colsum_det_route(R, C, VEC);
+  if (!r.flat && r.grid.x == 1) {
+    colsum_k<T, true><<<r.grid, 256, 0, s>>>(in, out, R, C);
+    return;
+  }
+  if (!scratch) {
+    fprintf(stderr, "colsum: deterministic mode needs its scratch\n");
+    abort();
+  }
+  if (r.flat) {
+    const size_t lds = (size_t)256 * r.ph * VEC * sizeof(float);
+    if (r.ph == 1)
+      colsum_flat_k<T, VEC, 1, true><<<r.grid, 256, lds, s>>>(in, scratch, R,
+                                                               C, r.rot);
+    else if (r.ph == 2)
+      colsum_flat_k<T, VEC, 2, true><<<r.grid, 256, lds, s>>>(in, scratch, R,
+                                                               C, r.rot);
+    else if (r.ph == 3)
+      colsum_flat_k<T, VEC, 3, true><<<r.grid, 256, lds, s>>>(in, scratch, R,
+                                                               C, r.rot);
+    else
+      colsum_flat_k<T, VEC, 4, true><<<r.grid, 256, lds, s>>>(in, scratch, R,
+                                                               C, r.rot);
+  } else {
+    colsum_k<T, true><<<r.grid, 256, 0, s>>>(in, scratch, R, C);
+  }
+  colsum_fin_k<<<dim3((unsigned)cdiv64(C, 16)), 256, 0, s>>>(
+      scratch, out, (int)r.grid.x, C, C);
+}
+
+extern "C" {
+
+// f32 scratch elements ps_colsum_* needs for [R][C] right now (0: none);
+// vec: elements per 16 B of the input type
+static int64_t colsum_scratch_elems(int64_t R, int C, int vec) {
+  if (!ps_deterministic()) return 0;
+  const ColsumDetRoute r = colsum_det_route(R, C, vec);
+  return r.flat || r.grid.x > 1 ? (int64_t)r.grid.x * C : 0;
+}
+int64_t ps_colsum_scratch_elems(int64_t R, int C, int bf16) {
+  return colsum_scratch_elems(R, C, bf16 ? 8 : 4);
+}
+
+void ps_colsum_f32(const float* in, float* out, int64_t R, int C,
+                   float* scratch, hipStream_t s) {
+  if (ps_deterministic())
+    return colsum_det<float, 4>(in, out, R, C, scratch, s);
   // flat path: big matrices (amortizes the LDS flush) OR small-R wide-C
   // (the banded kernel's row-slab grid collapses to R/64 blocks: an fc
   // bias grad at R=256 ran 4 workgroups)
   if (C % 4 == 0 && C <= 8192 && (R * C >= (8 << 20) || (R < 1024 && C >= 512)))
     PS_COLSUM_FLAT(float, 4, in);
   else
-    colsum_k<float><<<colsum_grid(R, C), 256, 0, s>>>(in, out, R, C);
+    colsum_banded<float>(in, out, R, C, s);
 }
-void ps_colsum_bf16(const void* in, float* out, int64_t R, int C, hipStream_t s) {
+void ps_colsum_bf16(const void* in, float* out, int64_t R, int C,
+                    float* scratch, hipStream_t s) {
+  if (ps_deterministic())
+    return colsum_det<__bf16, 8>((const __bf16*)in, out, R, C, scratch, s);
   if (C % 8 == 0 && C <= 8192 && (R * C >= (8 << 20) || (R < 1024 && C >= 512)))
     PS_COLSUM_FLAT(__bf16, 8, (const __bf16*)in);
   else
-    colsum_k<__bf16><<<colsum_grid(R, C), 256, 0, s>>>((const __bf16*)in, out, R, C);
+    colsum_banded<__bf16>((const __bf16*)in, out, R, C, s);
 }
 
+// scratch: [nchunks][max_c] floats, deterministic mode only
 void ps_colsum_mt(const void* descs, const void* chunks, int nchunks,
-                  int bf16, int max_c, hipStream_t s) {
+                  int bf16, int max_c, int ntensors, float* scratch,
+                  hipStream_t s) {
   if (nchunks <= 0) return;
+  if (ps_deterministic()) {
+    if (!scratch) {
+      fprintf(stderr, "colsum_mt: deterministic mode needs its scratch\n");
+      abort();
+    }
+    if (bf16)
+      colsum_mt_det_k<__bf16><<<dim3((unsigned)nchunks), 256, 0, s>>>(
+          (const ColsumDesc*)descs, (const ColsumChunk*)chunks, scratch,
+          max_c);
+    else
+      colsum_mt_det_k<float><<<dim3((unsigned)nchunks), 256, 0, s>>>(
+          (const ColsumDesc*)descs, (const ColsumChunk*)chunks, scratch,
+          max_c);
+    colsum_mt_fin_k<<<dim3((unsigned)ntensors), 256, 0, s>>>(
+        (const ColsumDesc*)descs, (const ColsumChunk*)chunks, nchunks,
+        scratch, max_c);
+    return;
+  }
+  ps_count_float_atomic();
   const size_t lds = (size_t)max_c * sizeof(float);
   if (bf16)
     colsum_mt_k<__bf16><<<dim3((unsigned)nchunks), 256, lds, s>>>(

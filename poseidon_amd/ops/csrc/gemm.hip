@@ -40,8 +40,10 @@
 // conv_layer.cu:25-121, inner_product_layer.cu:18-63).
 
 #include <algorithm>
+#include <atomic>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <type_traits>
 
 #include "ps_common.h"
@@ -863,7 +865,17 @@ __device__ inline bf16x8 tr_panel_frag(unsigned lds_base, int kk, int cb,
   }
 }
 
-template <int BM2, int BN2, int WGM2, int WGN2, bool SPLITK,
+// SPLITK: how a block's K slice reaches C.
+//   TR_NOSPLIT  one block per tile, plain stores of alpha * acc
+//   TR_ATOMIC   atomicAdd of alpha * acc into the zeroed C
+//   TR_WS       deterministic mode: C is the f32 workspace [splitk][M][N] and
+//               the block stores its raw partial into slab bz (ldC unused);
+//               splitk_reduce_tr_k sums the slabs in order and applies alpha.
+//               Padded bz blocks and dead waves store nothing, so only slabs
+//               < splitk and columns < N are ever read back.
+enum { TR_NOSPLIT = 0, TR_ATOMIC = 1, TR_WS = 2 };
+
+template <int BM2, int BN2, int WGM2, int WGN2, int SPLITK,
           bool GB2 = false>
 __global__ __launch_bounds__(256)
 void gemm_tn_tr_kernel(const __bf16* __restrict__ A,
@@ -877,7 +889,8 @@ void gemm_tn_tr_kernel(const __bf16* __restrict__ A,
   __shared__ __attribute__((aligned(16))) __bf16 b_lds[2][64 * BN2];
   // (by, bz) groups clustered per XCD when split, else the linear swizzle;
   // a padded bz exits via the k_begin >= k_end guard below
-  const GemmBlock blk = ps_remap_tr(SPLITK, gridDim.x, gridDim.y, gridDim.z,
+  const GemmBlock blk = ps_remap_tr(SPLITK != TR_NOSPLIT, gridDim.x,
+                                    gridDim.y, gridDim.z,
                                     blockIdx.x, blockIdx.y, blockIdx.z);
   const int bx = blk.bx, by = blk.by, bz = blk.bz;
   const int tid = threadIdx.x;
@@ -904,7 +917,7 @@ void gemm_tn_tr_kernel(const __bf16* __restrict__ A,
   // would push every re-read to HBM), and the stream is too big to be
   // cache-resident anyway (small colT matrices are L2/L3-HOT from the
   // im2col that just wrote them; nt measured -4% on AlexNet/GoogLeNet)
-  const bool ntb = SPLITK && gridDim.y == 1 && !GB2 &&
+  const bool ntb = SPLITK != TR_NOSPLIT && gridDim.y == 1 && !GB2 &&
                    (int64_t)K * N * 2 > (192LL << 20);
   if (ntb)
     stage_panel_tr<BN2, GB2, true>(b_lds[0], B, ldB, k_begin, n0, N, wid,
@@ -978,12 +991,42 @@ void gemm_tn_tr_kernel(const __bf16* __restrict__ A,
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int row = m0 + wm + fm * 16 + (lane >> 4) * 4 + r;
-        if (SPLITK)
+        if (SPLITK == TR_WS)
+          C[((int64_t)bz * M + row) * N + col] = acc[fm][fn][r];
+        else if (SPLITK == TR_ATOMIC)
           atomicAdd(&C[(int64_t)row * ldC + col], alpha * acc[fm][fn][r]);
         else
           C[(int64_t)row * ldC + col] = alpha * acc[fm][fn][r];
       }
     }
+}
+
+// Ordered combine of the TR_WS slabs: C[row][col] = alpha * (ws[0] + ws[1] +
+// ... + ws[splitk - 1]) over the M x N interior, slabs added in ascending
+// order whatever order their blocks ran in. N % 64 == 0, so the slabs are
+// read as float4; C is stored as float4 when its rows allow (VST).
+template <bool VST>
+__global__ void splitk_reduce_tr_k(const float* __restrict__ ws,
+                                   float* __restrict__ C, int M, int N,
+                                   int64_t ldc, int splitk, float alpha) {
+  const int N4 = N / 4;
+  const int64_t MN4 = (int64_t)M * N4;
+  const f32x4* ws4 = (const f32x4*)ws;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < MN4;
+       i += (int64_t)gridDim.x * blockDim.x) {
+    f32x4 v = ws4[i];
+    for (int s = 1; s < splitk; ++s) v += ws4[s * MN4 + i];
+    v *= alpha;
+    const int64_t row = i / N4;
+    const int col = (int)(i - row * N4) * 4;
+    float* out = C + row * ldc + col;
+    if (VST) {
+      *(f32x4*)out = v;
+    } else {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) out[e] = v[e];
+    }
+  }
 }
 
 // ---------------------------------------------------------------------------
@@ -1026,7 +1069,28 @@ static GemmShape gemm_shape(const GemmArgs& g) {
   sh.gather_b = g.gather_b != nullptr;
   sh.nt = g.a_klast && g.b_klast;
   sh.only128 = !g.a_klast && g.b_klast;
+  sh.deterministic = ps_deterministic() != 0;
   return sh;
+}
+
+// Deterministic mode (ps_set_deterministic) and the count of launches that
+// add floats atomically (ps_float_atomic_launches): process-wide, shared by
+// every translation unit's launchers.
+static std::atomic<int> g_deterministic{[] {
+  const char* e = getenv("PS_DETERMINISTIC");
+  return e && *e && strcmp(e, "0") != 0 ? 1 : 0;
+}()};
+static std::atomic<int64_t> g_float_atomic_launches{0};
+
+// a launcher about to take an atomic-float path: counted, and fatal in
+// deterministic mode (the bindings raise before it comes to this)
+static void float_atomic_launch(const char* what) {
+  if (ps_deterministic()) {
+    fprintf(stderr, "%s: atomic float path taken in deterministic mode\n",
+            what);
+    abort();
+  }
+  ps_count_float_atomic();
 }
 
 // tests / tuning only (ps_gemm_set_tr_tune); all zero in the training path
@@ -1156,27 +1220,50 @@ static void gemm_dispatch(const GemmArgs& g, const GemmPlan& p, float* ws,
 static void run_gemm_generic(const GemmArgs& g, const GemmPlan& p, float* ws,
                              hipStream_t s) {
   if (p.ws_elems == 0) ws = nullptr;
-  if (p.splitk > 1 && !ws) zero_c_for_atomics(g, s);
+  if (p.splitk > 1 && !ws) {
+    float_atomic_launch("gemm split-K");
+    zero_c_for_atomics(g, s);
+  }
   if (!g.in_bf16) gemm_dispatch<float, float>(g, p, ws, s);
   else if (g.out_f32) gemm_dispatch<__bf16, float>(g, p, ws, s);
   else gemm_dispatch<__bf16, __bf16>(g, p, ws, s);
 }
 
-static void run_gemm_tn_tr(const GemmArgs& g, const GemmPlan& p,
+// run-time tr16 split mode -> template argument
+template <typename F>
+static void with_tr_mode(int mode, F&& f) {
+  if (mode == TR_WS) f(std::integral_constant<int, TR_WS>{});
+  else if (mode == TR_ATOMIC) f(std::integral_constant<int, TR_ATOMIC>{});
+  else f(std::integral_constant<int, TR_NOSPLIT>{});
+}
+
+static void run_gemm_tn_tr(const GemmArgs& g, const GemmPlan& p, float* ws,
                            hipStream_t s) {
   const int M0 = p.M0, N0 = p.N0;
-  if (p.splitk > 1) zero_c_for_atomics(g, s);
+  const int mode = p.splitk == 1  ? TR_NOSPLIT
+                   : p.ws_elems > 0 ? TR_WS
+                                    : TR_ATOMIC;
+  if (mode == TR_WS && !ws) {
+    fprintf(stderr, "tr16 gemm: the plan's split-K workspace is missing\n");
+    abort();
+  }
+  if (mode == TR_ATOMIC) {
+    float_atomic_launch("tr16 gemm split-K");
+    zero_c_for_atomics(g, s);
+  }
+  // TR_WS: the kernel writes slabs, the reduce below overwrites C's interior
+  float* out = mode == TR_WS ? ws : (float*)g.C;
   // ceil: a bn = 128 grid runs its last column tile ragged (N0 % 64 == 0);
   // grid.z padded: enables L2 clustering
   dim3 grid((N0 + p.bn - 1) / p.bn, M0 / p.bm, ps_tr_grid_z(p));
   GatherDesc gb = g.gather_b ? *g.gather_b : GatherDesc{};
 #define PS_TR_CASE(BM_, BN_, WGM_, WGN_)                                    \
   if (p.bm == BM_ && p.bn == BN_)                                           \
-    with_bool(p.splitk > 1, [&](auto sk) {                                  \
+    with_tr_mode(mode, [&](auto sk) {                                       \
       with_bool(g.gather_b != nullptr, [&](auto gat) {                      \
         gemm_tn_tr_kernel<BM_, BN_, WGM_, WGN_, decltype(sk)::value,        \
                           decltype(gat)::value><<<grid, 256, 0, s>>>(       \
-            (const __bf16*)g.A, (const __bf16*)g.B, (float*)g.C, M0, N0,    \
+            (const __bf16*)g.A, (const __bf16*)g.B, out, M0, N0,            \
             g.K, g.lda, g.ldb, g.ldc, g.alpha, p.kchunk, gb);               \
       });                                                                   \
     });                                                                     \
@@ -1186,6 +1273,17 @@ static void run_gemm_tn_tr(const GemmArgs& g, const GemmPlan& p,
     abort();
   }
 #undef PS_TR_CASE
+  if (mode == TR_WS) {
+    int64_t rb = cdiv64((int64_t)M0 * N0 / 4, 256);
+    if (rb > 2048) rb = 2048;
+    float* c = (float*)g.C;
+    if (g.ldc % 4 == 0 && ((uintptr_t)c & 15) == 0)
+      splitk_reduce_tr_k<true><<<dim3((unsigned)rb), 256, 0, s>>>(
+          ws, c, M0, N0, g.ldc, p.splitk, g.alpha);
+    else
+      splitk_reduce_tr_k<false><<<dim3((unsigned)rb), 256, 0, s>>>(
+          ws, c, M0, N0, g.ldc, p.splitk, g.alpha);
+  }
   // edge strips [0,M) x [N0,N) and [M0,M) x [0,N0): unsplit generic
   // sub-problems (plain stores over the zeroed C)
   auto strip = [&](GemmArgs gt) {
@@ -1217,6 +1315,14 @@ void ps_gemm_plan(const GemmArgs* g, GemmPlan* plan) {
   if (!ps_tn_tr_plan(sh, g_tr_tune, plan)) ps_generic_plan(sh, plan);
 }
 
+void ps_set_deterministic(int on) { g_deterministic.store(on ? 1 : 0); }
+int ps_deterministic() { return g_deterministic.load(); }
+void ps_count_float_atomic() { g_float_atomic_launches.fetch_add(1); }
+int64_t ps_float_atomic_launches(int reset) {
+  return reset ? g_float_atomic_launches.exchange(0)
+               : g_float_atomic_launches.load();
+}
+
 void ps_gemm_set_tr_tune(int bm, int bn, int target) {
   g_tr_tune = {bm, bn, target};
 }
@@ -1224,7 +1330,7 @@ void ps_gemm_set_tr_tune(int bm, int bn, int target) {
 // ws: plan->ws_elems floats (null when the plan asks for none)
 void ps_gemm_run(const GemmArgs* g, const GemmPlan* plan, float* ws,
                  hipStream_t s) {
-  if (plan->tr16) return run_gemm_tn_tr(*g, *plan, s);
+  if (plan->tr16) return run_gemm_tn_tr(*g, *plan, ws, s);
   run_gemm_generic(*g, *plan, ws, s);
 }
 

@@ -511,6 +511,7 @@ void ps_lrn_bwd_v8_tail_f32(const float* x, const float* y, const float* dy,
                             float* db, int relu, int64_t rows, int C, int size,
                             float alpha, float beta, int max_blocks,
                             hipStream_t s) {
+  bias_flush_launch(db, "lrn_bwd_v8_tail");
   lrn_bwd_v8_any<float>(x, y, dy, mask, g, dx, db, relu != 0, rows, C, size,
                         alpha, beta, max_blocks, s);
 }
@@ -519,6 +520,7 @@ void ps_lrn_bwd_v8_tail_bf16(const void* x, const void* y, const void* dy,
                              float* db, int relu, int64_t rows, int C,
                              int size, float alpha, float beta, int max_blocks,
                              hipStream_t s) {
+  bias_flush_launch(db, "lrn_bwd_v8_tail");
   lrn_bwd_v8_any<__bf16>((const __bf16*)x, (const __bf16*)y, (const __bf16*)dy,
                          mask, g, (__bf16*)dx, db, relu != 0, rows, C, size,
                          alpha, beta, max_blocks, s);

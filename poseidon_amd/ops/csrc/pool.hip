@@ -284,11 +284,13 @@ void ps_maxpool_bwd_f32(const float* dy, const uint8_t* mask, float* dx,
 void ps_maxpool_bwd_tail_f32(const float* dy, const uint8_t* mask,
                              const float* x, float* dx, float* db,
                              const PoolGeom* g, int max_blocks, hipStream_t s) {
+  bias_flush_launch(db, "maxpool_bwd_tail");
   maxpool_bwd_tail<float, 4>(dy, mask, x, dx, db, *g, max_blocks, s);
 }
 void ps_maxpool_bwd_tail_bf16(const void* dy, const uint8_t* mask,
                               const void* x, void* dx, float* db,
                               const PoolGeom* g, int max_blocks, hipStream_t s) {
+  bias_flush_launch(db, "maxpool_bwd_tail");
   maxpool_bwd_tail<__bf16, 8>((const __bf16*)dy, mask, (const __bf16*)x,
                               (__bf16*)dx, db, *g, max_blocks, s);
 }

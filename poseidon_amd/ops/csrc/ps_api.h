@@ -41,6 +41,16 @@ void ps_gemm_run(const GemmArgs* g, const GemmPlan* plan, float* ws,
 // tests / tuning: force the tr16 tile and split-K block target (0 = planner)
 void ps_gemm_set_tr_tune(int bm, int bn, int target);
 
+// Deterministic mode, process-wide (initially PS_DETERMINISTIC=1): every
+// float reduction runs in an order fixed by the shape and the plan. No
+// launcher takes an atomic-float path while it is on.
+void ps_set_deterministic(int on);
+int ps_deterministic();
+// Host-side count of launched kernel instantiations that add floats
+// atomically (LDS or global): each launcher calls ps_count_float_atomic.
+void ps_count_float_atomic();
+int64_t ps_float_atomic_launches(int reset);
+
 // elementwise.hip
 void ps_relu_fwd_f32(const float*, float*, int64_t, float, hipStream_t);
 void ps_relu_bwd_f32(const float*, const float*, float*, int64_t, float, hipStream_t);
@@ -54,7 +64,11 @@ void ps_dropout_fwd_f32(const float*, float*, uint8_t*, int64_t, float,
                         uint64_t, uint64_t, hipStream_t);
 void ps_dropout_bwd_f32(const float*, const uint8_t*, float*, int64_t, float,
                         hipStream_t);
-void ps_colsum_f32(const float*, float*, int64_t, int, hipStream_t);
+// out[c] += column sums of in[R][C]. scratch: ps_colsum_scratch_elems(R, C)
+// floats (deterministic mode's [blocks][C] partials; null when that is 0)
+int64_t ps_colsum_scratch_elems(int64_t R, int C, int bf16);
+void ps_colsum_f32(const float*, float*, int64_t, int, float* scratch,
+                   hipStream_t);
 void ps_relu_fwd_bf16(const void*, void*, int64_t, float, hipStream_t);
 void ps_relu_bwd_bf16(const void*, const void*, void*, int64_t, float, hipStream_t);
 // slope-0 relu backward + bias colsum: (x, dy, dx, db, rows, C, max blocks)
@@ -72,8 +86,12 @@ void ps_dropout_fwd_bf16(const void*, void*, uint8_t*, int64_t, float,
                          uint64_t, uint64_t, hipStream_t);
 void ps_dropout_bwd_bf16(const void*, const uint8_t*, void*, int64_t, float,
                          hipStream_t);
-void ps_colsum_bf16(const void*, float*, int64_t, int, hipStream_t);
-void ps_colsum_mt(const void*, const void*, int, int, int, hipStream_t);
+void ps_colsum_bf16(const void*, float*, int64_t, int, float* scratch,
+                    hipStream_t);
+// (descs, chunks, nchunks, bf16, max C, tensors, scratch [nchunks][max C] in
+// deterministic mode | null)
+void ps_colsum_mt(const void*, const void*, int, int, int, int, float*,
+                  hipStream_t);
 void ps_threshold_fwd_f32(const float*, float*, int64_t, float, hipStream_t);
 void ps_threshold_fwd_bf16(const void*, void*, int64_t, float, hipStream_t);
 void ps_eltwise_max_fwd_f32(const float*, const float*, float*, uint8_t*,
@@ -145,15 +163,18 @@ void ps_lrn_bwd_v8_tail_bf16(const void*, const void*, const void*,
 void ps_softmax_rows_f32(const float*, float*, int64_t, int, hipStream_t);
 void ps_softmax_bwd_rows_f32(const float*, const float*, float*, int64_t, int,
                              hipStream_t);
+// (x, labels, prob, loss, row_loss, rows, C): loss += sum of -log p. With
+// row_loss (rows floats; required in deterministic mode) each row's term is
+// stored there and one block sums them in a fixed order into loss.
 void ps_softmax_loss_fwd_f32(const float*, const float*, float*, float*,
-                             int64_t, int, hipStream_t);
+                             float*, int64_t, int, hipStream_t);
 void ps_softmax_loss_bwd_f32(const float*, const float*, float*, int64_t, int,
                              float, hipStream_t);
 void ps_softmax_rows_bf16(const void*, void*, int64_t, int, hipStream_t);
 void ps_softmax_bwd_rows_bf16(const void*, const void*, void*, int64_t, int,
                               hipStream_t);
 void ps_softmax_loss_fwd_bf16(const void*, const float*, void*, float*,
-                              int64_t, int, hipStream_t);
+                              float*, int64_t, int, hipStream_t);
 void ps_softmax_loss_bwd_bf16(const void*, const float*, void*, int64_t, int,
                               float, hipStream_t);
 

@@ -9,6 +9,8 @@
 // the ReLU mask -- so the fused dx is bit-identical to the chain's.
 #pragma once
 
+#include <cstdlib>
+
 #include "ps_common.h"
 #include "ps_api.h"
 
@@ -77,6 +79,19 @@ __device__ inline void bias_sum_flush(float* part, const float* acc, int c0,
   }
   __syncthreads();
   for (int c = threadIdx.x; c < C; c += blockDim.x) atomicAdd(&db[c], part[c]);
+}
+
+// Host side of a launch that ends in bias_sum_flush (db != null): counted as
+// an atomic-float launch. Deterministic mode has no such launch -- the
+// bindings run the tail without db and sum the stored dx with the ordered
+// colsum instead -- so reaching here with the mode on is fatal.
+static inline void bias_flush_launch(const float* db, const char* what) {
+  if (!db) return;
+  if (ps_deterministic()) {
+    fprintf(stderr, "%s: atomic bias flush in deterministic mode\n", what);
+    abort();
+  }
+  ps_count_float_atomic();
 }
 
 // Grid of a flat grid-stride kernel over nvec V-wide chunks (CV per row)

@@ -14,7 +14,9 @@
 // e.g. conv wgrad) either accumulates atomically into C -- the launcher
 // zeroes C itself unless c_prezeroed -- or, when ws_elems > 0, stores
 // partials into a caller-allocated f32 workspace of that many elements and
-// reduces. A workspace is only consumed by the path that sized it.
+// reduces. A workspace is only consumed by the path that sized it. The tr16
+// path plans a workspace in deterministic mode only: [splitk][M0][N0] slabs
+// that a second kernel sums in slice order.
 struct GemmPlan {
   bool tr16;         // bf16 TN ds_read_b64_tr_b16 path (else generic tiles)
   int splitk;        // 1: no split
@@ -36,6 +38,9 @@ struct GemmShape {
   bool gather_b;   // B is gathered (implicit wgrad): no edge strips
   bool nt;         // both operands K-last: the N-fitting tiles exist
   bool only128;    // A K-major x B K-last (test entry only): 128x128 only
+  // deterministic mode: no plan may add into C atomically. A split takes
+  // the f32 workspace + ordered reduce (ws_elems > 0), or does not happen.
+  bool deterministic = false;
 };
 
 // Manual override of the tr16 tile and split-K block target, 0 = planner's
@@ -67,6 +72,9 @@ inline const TrTile* ps_tr_tile(int bm, int bn) {
     if (t.bm == bm && t.bn == bn) return &t;
   return nullptr;
 }
+
+// split-K workspaces (generic and tr16) stay under this many bytes
+constexpr int64_t PS_WS_CAP_BYTES = 256LL << 20;
 
 constexpr int PS_TR_BK = 64;                 // k rows per staged tile
 constexpr int PS_LDS_PER_CU = 160 * 1024;    // gfx950
@@ -281,7 +289,26 @@ inline bool ps_tn_tr_plan(const GemmShape& g, const TrTune& tune,
     if (M0 == bm && kchunk > kcap && g.K > kcap) kchunk = kcap;
     sk = (g.K + kchunk - 1) / kchunk;
   }
-  *p = {true, sk, 0, bm, bn, kchunk, M0, N0, 0, 0};
+  // Deterministic mode: the same split, but every slice stores its partial
+  // into slab bz of a [sk][M0][N0] workspace and a reduce kernel sums the
+  // slabs in order. The depth is the atomic plan's: a block's epilogue moves
+  // the same bm x bn floats either way, so the reasoning behind
+  // PS_TR_TALL_KMIN carries over, and the reduce reads sk * M0 * N0 floats
+  // once. Only the workspace cap can shrink it; sk = ceil(K / kchunk) keeps
+  // every slice non-empty.
+  int64_t ws_elems = 0;
+  if (g.deterministic && sk > 1) {
+    const int64_t slab = (int64_t)M0 * N0;
+    const int64_t fit = PS_WS_CAP_BYTES / 4 / slab;
+    if (sk > fit) {
+      const int64_t want = fit < 1 ? 1 : fit;
+      kchunk = (int)(((g.K + want - 1) / want + 63) / 64 * 64);
+      sk = (g.K + kchunk - 1) / kchunk;
+    }
+    if (sk > 1) ws_elems = sk * slab;
+    else kchunk = g.K;
+  }
+  *p = {true, sk, ws_elems, bm, bn, kchunk, M0, N0, 0, 0};
   return true;
 }
 
@@ -341,7 +368,9 @@ inline void ps_generic_plan(const GemmShape& g, GemmPlan* p,
   const int64_t tiles =
       (int64_t)((g.M + p->bm - 1) / p->bm) * ((g.N + p->bn - 1) / p->bn);
   const bool thin = may_split && tiles < 384;
-  if (thin && g.atomic_ok && g.K >= 512) {
+  // deterministic mode: as if C could not take atomics -- deep-K shapes take
+  // the workspace branch below, the rest run unsplit
+  if (thin && g.atomic_ok && !g.deterministic && g.K >= 512) {
     // atomic split-K: no workspace, so split much deeper (chunk >= 256)
     // -- the un-split grid leaves most of the 256 CUs idle
     const int64_t a = (512 + tiles - 1) / tiles, b = (g.K + 255) / 256;
@@ -352,7 +381,7 @@ inline void ps_generic_plan(const GemmShape& g, GemmPlan* p,
     const int64_t a = (512 + tiles - 1) / tiles, b = (g.K + 2047) / 2048;
     int sk = (int)(a < b ? a : b);
     int64_t ws_elems = (int64_t)sk * g.M * g.N;
-    if (sk > 1 && ws_elems * 4 <= (256LL << 20)) {
+    if (sk > 1 && ws_elems * 4 <= PS_WS_CAP_BYTES) {
       p->splitk = sk;
       p->ws_elems = ws_elems;
     }

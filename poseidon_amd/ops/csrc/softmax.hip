@@ -4,7 +4,10 @@
 // Rows = N*H*W (NHWC spatial softmax) or batch (classifier logits);
 // the reduced dim (channels/classes) is contiguous.
 
+#include <cstdlib>
+
 #include "ps_common.h"
+#include "ps_api.h"
 
 namespace ps {
 
@@ -60,7 +63,9 @@ __global__ void softmax_bwd_rows_k(const T* y, const T* dy, T* dx,
 
 // fused: prob + per-row NLL, loss accumulated into loss_out[0] (pre-zeroed),
 // final normalization by batch on the host side wrapper (adds /n).
-template <typename T, typename LT>
+// ROWS (deterministic mode): loss_out is a rows-long buffer and row r's term
+// is stored at loss_out[r]; loss_sum_k adds them up in a fixed order.
+template <typename T, typename LT, bool ROWS = false>
 __global__ void softmax_loss_fwd_k(const T* x, const LT* labels, T* prob,
                                    float* loss_out, int64_t rows, int C) {
   int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -81,8 +86,45 @@ __global__ void softmax_loss_fwd_k(const T* x, const LT* labels, T* prob,
     int lbl = (int)to_f32(labels[row]);
     lbl = min(max(lbl, 0), C - 1);
     float logp = to_f32(xr[lbl]) - m - __logf(sum);
-    atomicAdd(loss_out, -logp);
+    if (ROWS) loss_out[row] = -logp;
+    else atomicAdd(loss_out, -logp);
   }
+}
+
+// One block: loss[0] += sum of row_loss[0 .. rows). Thread t adds rows t,
+// t + 256, ... in ascending order, then a fixed LDS tree joins the 256
+// partials -- the same order on every run.
+__global__ void loss_sum_k(const float* __restrict__ row_loss,
+                           float* __restrict__ loss, int64_t rows) {
+  __shared__ float part[256];
+  float v = 0.f;
+  for (int64_t r = threadIdx.x; r < rows; r += 256) v += row_loss[r];
+  part[threadIdx.x] = v;
+  __syncthreads();
+  for (int off = 128; off > 0; off >>= 1) {
+    if ((int)threadIdx.x < off) part[threadIdx.x] += part[threadIdx.x + off];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) loss[0] += part[0];
+}
+
+template <typename T>
+static void softmax_loss_fwd(const T* x, const float* labels, T* prob,
+                             float* loss, float* row_loss, int64_t rows,
+                             int C, hipStream_t s) {
+  if (row_loss) {
+    softmax_loss_fwd_k<T, float, true><<<cdiv64(rows, 4), 256, 0, s>>>(
+        x, labels, prob, row_loss, rows, C);
+    loss_sum_k<<<1, 256, 0, s>>>(row_loss, loss, rows);
+    return;
+  }
+  if (ps_deterministic()) {
+    fprintf(stderr, "softmax loss: deterministic mode needs row_loss\n");
+    abort();
+  }
+  ps_count_float_atomic();
+  softmax_loss_fwd_k<T, float><<<cdiv64(rows, 4), 256, 0, s>>>(
+      x, labels, prob, loss, rows, C);
 }
 
 // dx = (prob - onehot) * w  (w = loss_weight / batch)
@@ -121,16 +163,17 @@ void ps_softmax_bwd_rows_bf16(const void* y, const void* dy, void* dx,
       (const __bf16*)y, (const __bf16*)dy, (__bf16*)dx, rows, C);
 }
 void ps_softmax_loss_fwd_f32(const float* x, const float* labels, float* prob,
-                             float* loss_out, int64_t rows, int C, hipStream_t s) {
-  softmax_loss_fwd_k<float, float><<<cdiv64(rows, 4), 256, 0, s>>>(
-      x, labels, prob, loss_out, rows, C);
+                             float* loss_out, float* row_loss, int64_t rows,
+                             int C, hipStream_t s) {
+  softmax_loss_fwd<float>(x, labels, prob, loss_out, row_loss, rows, C, s);
 }
 void ps_softmax_loss_fwd_bf16(const void* x, const float* labels, void* prob,
-                              float* loss_out, int64_t rows, int C, hipStream_t s) {
+                              float* loss_out, float* row_loss, int64_t rows,
+                              int C, hipStream_t s) {
   // labels stay fp32: class indices above 256 are not exactly representable
   // in bf16's 8-bit mantissa
-  softmax_loss_fwd_k<__bf16, float><<<cdiv64(rows, 4), 256, 0, s>>>(
-      (const __bf16*)x, labels, (__bf16*)prob, loss_out, rows, C);
+  softmax_loss_fwd<__bf16>((const __bf16*)x, labels, (__bf16*)prob, loss_out,
+                           row_loss, rows, C, s);
 }
 void ps_softmax_loss_bwd_f32(const float* prob, const float* labels, float* dx,
                              int64_t rows, int C, float w, hipStream_t s) {

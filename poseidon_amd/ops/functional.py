@@ -17,6 +17,7 @@ Semantics mirror the reference layer math:
 from __future__ import annotations
 
 import math
+import os
 from typing import Optional, Tuple
 
 import torch
@@ -73,6 +74,56 @@ def set_packed_conv(on: bool) -> None:
 
 def conv_policy_epoch() -> int:
     return _conv_policy_epoch
+
+
+# Deterministic mode. The flag itself lives in the extension (one per
+# process, initially PS_DETERMINISTIC=1); without the extension -- CPU only,
+# where every reduction is ordered anyway -- it is kept here.
+_deterministic_cpu = os.environ.get("PS_DETERMINISTIC", "0") not in ("", "0")
+
+
+def set_deterministic(on: bool) -> None:
+    """Opt-in bit-reproducible mode: every float reduction of the HIP kernels
+    (split-K GEMMs, column sums, fused bias gradients, the softmax loss) runs
+    in an order fixed by the problem shape and the plan instead of by block
+    scheduling, so the same steps from the same seed on one GPU in one build
+    leave identical bits, eager or graphed. No kernel takes an atomic-float
+    path while it is on; a launch that has no ordered form raises. Toggling
+    bumps conv_policy_epoch() so nets re-plan their cached tables."""
+    global _deterministic_cpu, _conv_policy_epoch
+    on = bool(on)
+    if on == deterministic():
+        return
+    if ext_available():
+        _ext().set_deterministic(on)
+    _deterministic_cpu = on
+    _conv_policy_epoch += 1
+    from ..core.context import ctx
+    ctx().deterministic = on
+
+
+def deterministic() -> bool:
+    if ext_available():
+        return bool(_ext().deterministic())
+    return _deterministic_cpu
+
+
+def gemm_plan(M: int, N: int, K: int, a_klast: bool, b_klast: bool,
+              bf16: bool) -> dict:
+    """The launch plan of the test GEMM entry for this shape right now:
+    tr16, splitk, ws_elems, bm, bn, kchunk, grid_z."""
+    return dict(_ext().gemm_plan(int(M), int(N), int(K), bool(a_klast),
+                                 bool(b_klast), bool(bf16)))
+
+
+def float_atomic_launches(reset: bool = False) -> int:
+    """Launches so far of kernel instantiations that add floats atomically
+    (LDS or global). A host-side counter bumped at launch time: nothing is
+    read from the device. Stays put across any work done in deterministic
+    mode. reset=True also sets it back to zero."""
+    if not ext_available():
+        return 0
+    return int(_ext().float_atomic_launches(bool(reset)))
 
 
 def khwc_layout(Cg: int, kw: int, packed: bool) -> Tuple[int, int]:
@@ -669,13 +720,16 @@ def unpack_mt_run(mt) -> None:
 
 
 def colsum_mt_prepare(dys, dbs):
-    d, c, n, mc = _ext().colsum_mt_prepare(list(dys), list(dbs))
-    return d, c, int(n), int(mc)
+    """(descs, chunks, nchunks, max C, tensors, scratch). The scratch holds
+    deterministic mode's per-chunk partials and is sized only when the table
+    is prepared with the mode on: prepare again after toggling it."""
+    d, c, n, mc, nt, scratch = _ext().colsum_mt_prepare(list(dys), list(dbs))
+    return d, c, int(n), int(mc), int(nt), scratch
 
 
 def colsum_mt_run(mt, bf16: bool) -> None:
-    d, c, n, mc = mt
-    _ext().colsum_mt_run(d, c, n, bf16, mc)
+    d, c, n, mc, nt, scratch = mt
+    _ext().colsum_mt_run(d, c, n, bf16, mc, nt, scratch)
 
 
 def colsum_acc(dy, db) -> None:

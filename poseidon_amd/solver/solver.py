@@ -229,6 +229,14 @@ class SGDSolver:
         # offset counter) still advances during the warm-up.
         saved = [(t, t.clone()) for i in self.history
                  for t in (self.net.params[i].blob.data, self.history[i])]
+        # Deterministic mode promises graphed == eager bit for bit, so there
+        # the dropout counters are put back as well (a counter first made
+        # during the warm-up goes back to zero). Off, graphed runs keep the
+        # mask sequence they always had.
+        counters = [(l, None if l._offset_dev is None
+                     else l._offset_dev.clone())
+                    for l in self.net.layers
+                    if ops.deterministic() and hasattr(l, "_offset_dev")]
         # staged data layers: the warm-up and the capture all run on the
         # first batch and consume no further records; the first replay
         # trains on it
@@ -253,6 +261,12 @@ class SGDSolver:
         for t, t0 in saved:
             t.copy_(t0)
         del saved
+        for l, t0 in counters:
+            if l._offset_dev is not None:
+                if t0 is None:
+                    l._offset_dev.zero_()
+                else:
+                    l._offset_dev.copy_(t0)
         ok = True
         err: Optional[Exception] = None
         try:

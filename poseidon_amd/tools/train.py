@@ -41,6 +41,11 @@ def main(argv=None):
                     help="DATA / IMAGE_DATA layers ship raw uint8 records and "
                          "run mean/crop/mirror/scale on the device (default "
                          "off; PS_DEVICE_TRANSFORM=1 does the same)")
+    ap.add_argument("--deterministic", action="store_true",
+                    help="bit-reproducible float reductions on the GPU: the "
+                         "same seed gives the same bits on one GPU in one "
+                         "build (default off; PS_DETERMINISTIC=1 does the "
+                         "same; costs speed, see docs/performance.md)")
     ap.add_argument("--graph", action="store_true",
                     help="replay the training iteration from a hipGraph "
                          "(DB-backed data layers need --device-transform); "
@@ -60,7 +65,8 @@ def main(argv=None):
     pa.init(device="cuda" if use_gpu else "cpu",
             seed=seed if seed >= 0 else 1,
             compute_dtype=cd,
-            device_transform=True if args.device_transform else None)
+            device_transform=True if args.device_transform else None,
+            deterministic=True if args.deterministic else None)
 
     solver = get_solver(solver_param, use_sfb=args.svb)
     if args.weights:
