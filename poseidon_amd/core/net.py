@@ -114,6 +114,9 @@ class Net:
         self._colsum_mt = None   # deferred bias-colsum table
         self._colsum_prev_key = None
         self._repack_key = None
+        self._repack_entries: List = []  # (layer, master, wk, wkT, G, kw_ld, c_ld)
+        self._repack_lite = None  # (table without the marked fc shadows, key)
+        self._fc_marks = None     # [(layer, master, _version, shadow)]
         self._loss_marks: Dict[int, List] = {}
         # inter-branch stream parallelism (inception-style nets): built by
         # _build_stream_schedule, activated lazily on GPU
@@ -529,14 +532,23 @@ class Net:
             extra = [t for l in self.layers
                      if hasattr(l, "extra_zero_buffers")
                      for t in l.extra_zero_buffers()]
+            # A weight diff that its one writer overwrites in this backward
+            # (the solver marks those layers) is not zeroed: 0 + dW is dW.
+            # The identity key below follows the set.
+            skip = {id(l.blobs[0]) for l in self.layers
+                    if l.blobs and hasattr(l, "overwrites_dw")
+                    and l.overwrites_dw()}
+            zeroed = [b for b in owned if id(b) not in skip]
             if self._zero_mt is None and all(
                     b.has_diff() and b.diff.dtype == torch.float32
                     and b.diff.is_contiguous() for b in owned):
-                ts = [b.diff for b in owned] + extra
+                ts = [b.diff for b in zeroed] + extra
+                if not ts:
+                    return
                 self._zero_mt = (ops.zero_mt_prepare(ts), [id(t) for t in ts])
             if self._zero_mt is not None:
                 mt, ids = self._zero_mt
-                cur = [id(b.diff) for b in owned] + [id(t) for t in extra]
+                cur = [id(b.diff) for b in zeroed] + [id(t) for t in extra]
                 if cur == ids:
                     ops.zero_mt_run(mt)
                     return
@@ -556,8 +568,11 @@ class Net:
                  if getattr(l, "_unpack_pending", False)]
         if not convs:
             return
-        key = [(id(l._dwk_cache), id(l.blobs[0].diff), l._dwk_layout)
-               for l in convs]
+        # a conv the solver marked writes its (un-zeroed) diff; the others
+        # add to theirs
+        over = [l.overwrites_dw() for l in convs]
+        key = [(id(l._dwk_cache), id(l.blobs[0].diff), l._dwk_layout, o)
+               for l, o in zip(convs, over)]
         if self._unpack_mt is None or self._unpack_mt[1] != key:
             self._unpack_mt = (ops.unpack_mt_prepare(
                 [l._dwk_cache for l in convs],
@@ -566,7 +581,7 @@ class Net:
                 [l.blobs[0].data.shape[2] for l in convs],
                 [l.blobs[0].data.shape[3] for l in convs],
                 [l._dwk_layout[0] for l in convs],
-                [l._dwk_layout[1] for l in convs]), key)
+                [l._dwk_layout[1] for l in convs], over), key)
         ops.unpack_mt_run(self._unpack_mt[0])
         for l in convs:
             l._unpack_pending = False
@@ -594,11 +609,47 @@ class Net:
             for l, _ in pend:
                 l._pending_colsum = None
 
-    def _maybe_mt_repack(self) -> None:
+    # -- fc shadows kept current by the solver's update kernel -----------
+    def mark_fc_shadows_current(self, layers) -> None:
+        """The solver's update just wrote these INNER_PRODUCT layers' bf16
+        shadows from the new weights. Until a master changes again the
+        repack skips them (the table without them is built here, outside
+        any capture). The guard is torch's per-tensor _version: the update
+        kernel writes through raw pointers and leaves it alone, while
+        copy_ / load_weights / restore bump it."""
+        if self._repack_mt is None or not layers:
+            self._fc_marks = None
+            return
+        marks = [(l, l.blobs[0].data, l.blobs[0].data._version, l._wk_cache)
+                 for l in layers]
+        key = tuple(id(l) for l in layers)
+        if self._repack_lite is None or self._repack_lite[1] != key:
+            rest = [e for e in self._repack_entries
+                    if all(e[0] is not l for l in layers)]
+            mt = ops.repack_mt_prepare(*[[e[k] for e in rest]
+                                         for k in range(1, 7)]) \
+                if rest else None
+            self._repack_lite = (mt, key)
+        self._fc_marks = marks
+
+    def invalidate_fc_shadows(self) -> None:
+        self._fc_marks = None
+
+    def fc_shadows_current(self) -> bool:
+        """Whether every shadow the solver marked still matches its master:
+        same tensors, same versions."""
+        marks = self._fc_marks
+        return (marks is not None and ops.fused_weight_tail()
+                and all(l.blobs[0].data is m and m._version == v
+                        and l._wk_cache is sh for l, m, v, sh in marks))
+
+    def _maybe_mt_repack(self, full: bool = False) -> None:
         """One repack_mt kernel refreshes every conv's bf16 khwc shadow +
         dgrad transpose from the fp32 masters (GoogLeNet: 2 launches
         instead of 68 per step). Buffers are persistent per layer; the
-        table is keyed on master identities (restore() rebuilds)."""
+        table is keyed on master identities (restore() rebuilds). While the
+        fc shadows the solver marked are current (and full is False) the
+        table without them runs instead."""
         if ctx().device != "cuda" or ctx().compute_dtype != torch.bfloat16:
             return
         convs = [l for l in self.layers
@@ -658,6 +709,16 @@ class Net:
             self._repack_mt = ops.repack_mt_prepare(masters, wks, wkTs, Gs,
                                                     kw_lds, c_lds)
             self._repack_key = key
+            # new shadow buffers: nothing the solver wrote is in them
+            self._repack_entries = list(zip(convs + ips, masters, wks, wkTs,
+                                            Gs, kw_lds, c_lds))
+            self._repack_lite = None
+            self._fc_marks = None
+        if not full and self.fc_shadows_current():
+            if self._repack_lite[0] is not None:
+                ops.repack_mt_run(self._repack_lite[0])
+            return
+        self._fc_marks = None
         ops.repack_mt_run(self._repack_mt)
 
     def forward(self, start: int = 0, end: Optional[int] = None) -> float:

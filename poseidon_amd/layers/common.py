@@ -11,6 +11,7 @@ exposed for the solver's all-gather + MFMA outer-product reconstruction
 
 from __future__ import annotations
 
+import os
 from typing import Optional, Tuple
 
 import torch
@@ -48,6 +49,19 @@ class InnerProductLayer(Layer):
         # SFB: when set by the distributed solver, backward defers the dW GEMM
         self.sfb_active = False
         self.sfb_factors: Optional[Tuple[torch.Tensor, torch.Tensor]] = None
+        # set by the solver for a weight this layer alone writes once per
+        # backward: the dW GEMM then writes the diff (beta=0) instead of a
+        # temporary that is added into a zeroed diff -- the same bits
+        self.dw_overwrite = False
+
+    def overwrites_dw(self) -> bool:
+        """Whether this backward writes the weight diff instead of adding to
+        it (the net then leaves that diff out of its zero table)."""
+        d = self.blobs[0]
+        return (self.dw_overwrite and not self.sfb_active
+                and ops.fused_weight_tail() and d.data.is_cuda
+                and d.data.dtype == torch.float32
+                and os.environ.get("PS_DW_ACC", "0") != "1")
 
     def reshape(self, bottom, top) -> None:
         self.M = bottom[0].num
@@ -75,16 +89,19 @@ class InnerProductLayer(Layer):
                 and self.blobs[0].diff.dtype == torch.float32
                 and _os.environ.get("PS_DW_ACC", "0") == "1"):
             dw_acc = self.blobs[0].diff.view(self.N, self.K)
+        dw_out = None
+        if dw_acc is None and need_dw and self.overwrites_dw():
+            dw_out = self.blobs[0].diff.view(self.N, self.K)
         dx, dw, db = ops.linear_backward(
             x, self.blobs[0].data.view(self.N, self.K), dy,
             need_dx=propagate_down[0], need_dw=need_dw,
             has_bias=self.bias_term, w_shadow=self._wk_cache,
-            dw_acc=dw_acc)
+            dw_acc=dw_acc, dw_out=dw_out)
         if self.sfb_active:
             # Sufficient factors a=dy [M,N], b=x [M,K]; ∇W = aᵀ·b is
             # reconstructed after the all-gather (solver/sfb.py).
             self.sfb_factors = (dy, x)
-        elif dw_acc is None:
+        elif dw_acc is None and dw_out is None:
             self.blobs[0].diff.view(self.N, self.K).add_(dw)
         if self.bias_term:
             self.blobs[1].diff.view(-1).add_(db)

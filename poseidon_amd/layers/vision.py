@@ -77,6 +77,17 @@ class ConvolutionLayer(Layer):
             filler.fill(b, cp.bias_filler if cp.has("bias_filler") else None)
             self.blobs.append(b)
 
+    def overwrites_dw(self) -> bool:
+        """Whether this backward's deferred unpack writes the weight diff
+        instead of adding to it (the net then leaves that diff out of its
+        zero table). dw_overwrite is set by the solver for a single-bottom
+        conv whose weight no other layer shares; the first backward, which
+        has no persistent scratch yet and unpacks in the call, still adds."""
+        return (getattr(self, "dw_overwrite", False)
+                and getattr(self, "defer_unpack", False)
+                and self._dwk_cache is not None
+                and ops.fused_weight_tail())
+
     def reshape(self, bottom: List[Blob], top: List[Blob]) -> None:
         n, c, h, w = bottom[0].shape
         ho = ops.conv_out_size(h, self.kernel[0], self.pad[0], self.stride[0])

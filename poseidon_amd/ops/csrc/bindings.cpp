@@ -283,8 +283,11 @@ std::vector<c10::optional<Tensor>> linear_backward(
     const Tensor& x, const Tensor& w, const Tensor& dy,
     bool need_dx, bool need_dw, bool has_bias,
     const c10::optional<Tensor>& w_shadow,
-    const c10::optional<Tensor>& dw_acc) {
+    const c10::optional<Tensor>& dw_acc,
+    const c10::optional<Tensor>& dw_out) {
   check_float_like(dy, "dy");
+  TORCH_CHECK(!(dw_acc.has_value() && dw_out.has_value()),
+              "linear_backward: dw_acc and dw_out exclude each other");
   auto xc = x.contiguous();
   auto wc = linear_weight(w, w_shadow, is_bf16(dy));
   auto dyc = dy.contiguous();
@@ -301,14 +304,23 @@ std::vector<c10::optional<Tensor>> linear_backward(
     // dW[N,K] = dy^T[N,M] @ x[M,K]: contraction M; both K-major; fp32 out.
     // With dw_acc, accumulate straight into the param diff (beta=1): saves
     // the separate diff.add_(dw) pass over the fc weights (VGG: a 138M
-    // element read-modify-write per step)
-    Tensor t = dw_acc.has_value()
-                   ? *dw_acc
+    // element read-modify-write per step). With dw_out, WRITE the param
+    // diff (beta=0): for a weight with one writer per backward that is the
+    // same bits as adding into a zeroed diff, without the zero pass, the
+    // temporary and the add. The target's old contents are never read: a
+    // split-K plan clears or workspaces its own target.
+    const bool own = !dw_acc.has_value() && !dw_out.has_value();
+    Tensor t = dw_acc.has_value() ? *dw_acc
+               : dw_out.has_value()
+                   ? *dw_out
                    : at::empty({N, K}, x.options().dtype(at::kFloat));
-    TORCH_CHECK(t.scalar_type() == at::kFloat && t.is_contiguous());
+    TORCH_CHECK(t.is_cuda() && t.scalar_type() == at::kFloat &&
+                t.is_contiguous() && t.dim() == 2 && t.size(0) == N &&
+                t.size(1) == K,
+                "linear_backward: dW target must be contiguous f32 [N,K]");
     run_gemm(dyc, xc, t, nullptr, N, K, M, N, K, K, 0, 0, 0, false, false,
              1.0f, dw_acc.has_value() ? 1.0f : 0.0f);
-    if (!dw_acc.has_value()) dw = t;
+    if (own) dw = t;
   }
   if (has_bias) {
     Tensor t = at::zeros({N}, x.options().dtype(at::kFloat));
@@ -1317,10 +1329,15 @@ std::vector<Tensor> sgd_mt_prepare(std::vector<Tensor> ws,
                                    std::vector<Tensor> gs,
                                    std::vector<Tensor> hs,
                                    std::vector<double> lr_mults,
-                                   std::vector<double> wds) {
+                                   std::vector<double> wds,
+                                   std::vector<c10::optional<Tensor>> shadows) {
   const size_t nt = ws.size();
   TORCH_CHECK(gs.size() == nt && hs.size() == nt && lr_mults.size() == nt &&
               wds.size() == nt, "sgd_mt_prepare: length mismatch");
+  // bf16 shadows the update keeps current, one entry (or None) per tensor;
+  // empty = none
+  TORCH_CHECK(shadows.empty() || shadows.size() == nt,
+              "sgd_mt_prepare: shadows length mismatch");
   std::vector<ps::MTDesc> descs(nt);
   for (size_t t = 0; t < nt; ++t) {
     TORCH_CHECK(ws[t].is_cuda() && ws[t].is_contiguous() &&
@@ -1329,9 +1346,20 @@ std::vector<Tensor> sgd_mt_prepare(std::vector<Tensor> ws,
                 "sgd_mt_prepare: params must be contiguous f32 CUDA");
     int64_t n = ws[t].numel();
     TORCH_CHECK(gs[t].numel() == n && hs[t].numel() == n);
+    void* shadow = nullptr;
+    if (!shadows.empty() && shadows[t].has_value()) {
+      const Tensor& sh = *shadows[t];
+      // the vec4 body stores four bf16 at once: 8-byte alignment
+      TORCH_CHECK(sh.is_cuda() && sh.is_contiguous() &&
+                  sh.scalar_type() == at::kBFloat16 && sh.numel() == n &&
+                  (uintptr_t)sh.data_ptr() % 8 == 0,
+                  "sgd_mt_prepare: a shadow must be contiguous bf16 CUDA "
+                  "with its tensor's element count");
+      shadow = sh.data_ptr();
+    }
     descs[t] = {ws[t].data_ptr<float>(), gs[t].data_ptr<float>(),
                 hs[t].data_ptr<float>(), n, (float)lr_mults[t],
-                (float)wds[t]};
+                (float)wds[t], shadow};
   }
   return mt_tables(descs, ws[0], mt_by_elts);
 }
@@ -1425,12 +1453,16 @@ std::vector<Tensor> unpack_mt_prepare(std::vector<Tensor> dwks,
                                       std::vector<int64_t> khs,
                                       std::vector<int64_t> kws,
                                       std::vector<int64_t> kw_lds,
-                                      std::vector<int64_t> c_lds) {
+                                      std::vector<int64_t> c_lds,
+                                      std::vector<bool> overwrites) {
   const size_t nt = dwks.size();
   // khwc_layout() per tensor; empty = every conv plain (kw, Cig)
   TORCH_CHECK((kw_lds.empty() && c_lds.empty()) ||
               (kw_lds.size() == nt && c_lds.size() == nt),
               "unpack_mt_prepare: layout length mismatch");
+  // per tensor: write dw instead of adding to it; empty = all accumulate
+  TORCH_CHECK(overwrites.empty() || overwrites.size() == nt,
+              "unpack_mt_prepare: overwrites length mismatch");
   std::vector<ps::MTUnpackDesc> descs(nt);
   for (size_t t = 0; t < nt; ++t) {
     TORCH_CHECK(dwks[t].is_cuda() && dwks[t].scalar_type() == at::kFloat &&
@@ -1447,7 +1479,8 @@ std::vector<Tensor> unpack_mt_prepare(std::vector<Tensor> dwks,
                 (int64_t)khs[t] * kw_ld * c_ld <= ldk,
                 "unpack_mt_prepare: khwc layout exceeds the dwk row");
     descs[t] = {dwks[t].data_ptr<float>(), dws[t].data_ptr<float>(), n,
-                Co, (int)Cigs[t], (int)khs[t], (int)kws[t], ldk, kw_ld, c_ld};
+                Co, (int)Cigs[t], (int)khs[t], (int)kws[t], ldk, kw_ld, c_ld,
+                !overwrites.empty() && overwrites[t] ? 1 : 0};
   }
   return mt_tables(descs, dwks[0], mt_by_elts);
 }

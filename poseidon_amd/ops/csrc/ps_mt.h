@@ -25,6 +25,8 @@ struct MTDesc {  // SGD update
   int64_t n;
   float lr_mult;
   float wd;
+  void* shadow;  // bf16 copy of w in w's own flat layout, or null: written
+                 // from the registers that hold the new weight
 };
 
 struct MTZeroDesc {
@@ -50,6 +52,8 @@ struct MTUnpackDesc {
   int64_t n;         // Co*Cig*kh*kw
   int Co, Cig, kh, kw, ldk;
   int kw_ld, c_ld;   // dwk tap-row width / channel slots (ps_khwc_col)
+  int overwrite;     // dw = ... instead of dw += ... (single-writer diffs
+                     // that nobody zeroed)
 };
 
 // bias colsum; its chunks count ROWS (ColsumChunk.off = start row)

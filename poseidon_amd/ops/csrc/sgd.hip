@@ -79,6 +79,11 @@ __global__ void adagrad_update_k(float* w, const float* g, float* h,
 // ps_mt.h.
 // ---------------------------------------------------------------------------
 
+typedef __bf16 bf16x4v __attribute__((ext_vector_type(4)));
+
+// A desc with a shadow also stores the new weight as bf16, with the cast of
+// repack_mt_k's straight-cast branch: the fc forward of the next step reads
+// the same bits that repack would write, without the pass that re-reads w.
 template <bool LRDEV>
 __global__ void sgd_mt_k(const MTDesc* __restrict__ descs,
                          const MTChunk* __restrict__ chunks, float lr_scalar,
@@ -87,6 +92,7 @@ __global__ void sgd_mt_k(const MTDesc* __restrict__ descs,
   const MTDesc d = descs[ck.t];
   const float lr = (LRDEV ? lr_dev[0] : lr_scalar) * d.lr_mult;
   const float wd = d.wd;
+  __bf16* const sh = (__bf16*)d.shadow;
   int64_t i = ck.off + (int64_t)threadIdx.x * 4;
 #pragma unroll
   for (int it = 0; it < MT_CHUNK / (256 * 4); ++it, i += 256 * 4) {
@@ -101,11 +107,18 @@ __global__ void sgd_mt_k(const MTDesc* __restrict__ descs,
       }
       *(f32x4*)&d.w[i] = wv;
       *(f32x4*)&d.h[i] = hv;
+      if (sh) {
+        bf16x4v o = {(__bf16)wv[0], (__bf16)wv[1], (__bf16)wv[2],
+                     (__bf16)wv[3]};
+        *(bf16x4v*)(sh + i) = o;
+      }
     } else if (i < d.n) {
       for (int64_t k = i; k < d.n; ++k) {
         float hv = mom * d.h[k] + lr * (d.g[k] + wd * d.w[k]);
         d.h[k] = hv;
-        d.w[k] -= hv;
+        const float wn = d.w[k] - hv;
+        d.w[k] = wn;
+        if (sh) sh[k] = (__bf16)wn;
       }
     }
   }
@@ -124,7 +137,6 @@ __global__ void repack_mt_k(const MTRepackDesc* __restrict__ descs,
   if (KW == 1 && KH == 1 && d.G == 1 && !d.wkT && d.ldk == Cig) {
     // fc shadows: khwc degenerates to a straight cast -- skip the
     // per-element divides (VGG: 102M of 138M repacked elements)
-    typedef __bf16 bf16x4v __attribute__((ext_vector_type(4)));
     int64_t i = ck.off + (int64_t)threadIdx.x * 4;
 #pragma unroll
     for (int it = 0; it < MT_CHUNK / (256 * 4); ++it, i += 256 * 4) {
@@ -157,9 +169,11 @@ __global__ void repack_mt_k(const MTRepackDesc* __restrict__ descs,
 }
 
 // inverse of repack_mt_k for GRADIENTS: khwc fp32 wgrad scratch -> NCHW
-// fp32 param diff, accumulating (beta=1). One launch covers every conv's
-// unpack at the end of backward (GoogLeNet: 57 weight_from_khwc launches
-// -> 1) -- single-GPU mode only; DWBP needs per-layer grads final.
+// fp32 param diff, accumulating (beta=1) unless the desc says overwrite
+// (a diff with this one writer, which then nobody has to zero). One launch
+// covers every conv's unpack at the end of backward (GoogLeNet: 57
+// weight_from_khwc launches -> 1) -- single-GPU mode only; DWBP needs
+// per-layer grads final.
 __global__ void unpack_mt_k(const MTUnpackDesc* __restrict__ descs,
                             const MTChunk* __restrict__ chunks) {
   const MTChunk ck = chunks[blockIdx.x];
@@ -172,8 +186,9 @@ __global__ void unpack_mt_k(const MTUnpackDesc* __restrict__ descs,
     int kkh = (int)(t % KH); t /= KH;
     int ci = (int)(t % Cig);
     int co = (int)(t / Cig);
-    d.dw[i] += d.dwk[(int64_t)co * d.ldk +
-                     ps_khwc_col(kkh, kkw, ci, d.kw_ld, d.c_ld)];
+    const float v = d.dwk[(int64_t)co * d.ldk +
+                          ps_khwc_col(kkh, kkw, ci, d.kw_ld, d.c_ld)];
+    d.dw[i] = d.overwrite ? v : d.dw[i] + v;
   }
 }
 

@@ -108,6 +108,24 @@ def deterministic() -> bool:
     return _deterministic_cpu
 
 
+# The fused weight tail (docs/architecture.md): fc weight gradients are
+# written straight into the param diff, sole-owner diffs leave the zero
+# table, and the SGD kernel writes the fc bf16 shadows. Off reproduces the
+# accumulate / full-repack step bit for bit. Read at every step by the
+# layers, the net and the solver, so it may be flipped between eager steps;
+# a captured graph keeps what it was captured with.
+_fused_weight_tail = os.environ.get("PS_WEIGHT_TAIL", "1") not in ("", "0")
+
+
+def set_fused_weight_tail(on: bool) -> None:
+    global _fused_weight_tail
+    _fused_weight_tail = bool(on)
+
+
+def fused_weight_tail() -> bool:
+    return _fused_weight_tail
+
+
 def gemm_plan(M: int, N: int, K: int, a_klast: bool, b_klast: bool,
               bf16: bool) -> dict:
     """The launch plan of the test GEMM entry for this shape right now:
@@ -246,14 +264,23 @@ def linear_forward(x: torch.Tensor, w: torch.Tensor,
 def linear_backward(x: torch.Tensor, w: torch.Tensor, dy: torch.Tensor,
                     need_dx: bool, need_dw: bool, has_bias: bool,
                     w_shadow: Optional[torch.Tensor] = None,
-                    dw_acc: Optional[torch.Tensor] = None):
+                    dw_acc: Optional[torch.Tensor] = None,
+                    dw_out: Optional[torch.Tensor] = None):
     """dw_acc: fp32 [N,K] buffer the weight grad is ACCUMULATED into
-    (beta=1 GEMM); when set, the returned dw is None."""
+    (beta=1 GEMM). dw_out: fp32 contiguous [N,K] buffer the weight grad is
+    WRITTEN into (beta=0; its old contents are never read). With either,
+    the returned dw is None."""
     if dy.is_cuda:
         return _ext().linear_backward(x, w, dy, need_dx, need_dw, has_bias,
-                                      w_shadow, dw_acc)
+                                      w_shadow, dw_acc, dw_out)
     dx = dy.matmul(w) if need_dx else None
     dw = dy.t().matmul(x) if need_dw else None
+    if dw is not None and dw_out is not None:
+        dw_out.copy_(dw)
+        dw = None
+    elif dw is not None and dw_acc is not None:
+        dw_acc.add_(dw)
+        dw = None
     db = dy.sum(dim=0) if has_bias else None
     return dx, dw, db
 
@@ -666,13 +693,17 @@ def sgd_update(w: torch.Tensor, grad: torch.Tensor, hist: torch.Tensor,
 
 # -- multi-tensor apply: one launch for ALL params (GPU only) ---------------
 
-def sgd_mt_prepare(ws, gs, hs, lr_mults, wds):
+def sgd_mt_prepare(ws, gs, hs, lr_mults, wds, shadows=None):
     """Build device-resident descriptor/chunk tables for sgd_mt_run. Shapes
     and tensor identities must stay fixed afterwards (they do: param blobs
-    are allocated once at net build)."""
+    are allocated once at net build). shadows: per tensor, a bf16 buffer of
+    the same element count that the update also writes the new weight to,
+    or None."""
     d, c, n = _ext().sgd_mt_prepare(list(ws), list(gs), list(hs),
                                     [float(v) for v in lr_mults],
-                                    [float(v) for v in wds])
+                                    [float(v) for v in wds],
+                                    list(shadows) if shadows is not None
+                                    else [])
     return d, c, int(n.item())
 
 
@@ -705,12 +736,16 @@ def repack_mt_run(mt) -> None:
     _ext().repack_mt_run(d, c, n)
 
 
-def unpack_mt_prepare(dwks, dws, Cigs, khs, kws, kw_lds=(), c_lds=()):
-    """kw_lds / c_lds: khwc_layout() of each dwk scratch; empty = plain."""
+def unpack_mt_prepare(dwks, dws, Cigs, khs, kws, kw_lds=(), c_lds=(),
+                      overwrites=()):
+    """kw_lds / c_lds: khwc_layout() of each dwk scratch; empty = plain.
+    overwrites: per tensor, write dw instead of adding to it; empty = every
+    tensor accumulates."""
     d, c, n = _ext().unpack_mt_prepare(list(dwks), list(dws), list(Cigs),
                                        list(khs), list(kws),
                                        [int(v) for v in kw_lds],
-                                       [int(v) for v in c_lds])
+                                       [int(v) for v in c_lds],
+                                       [bool(v) for v in overwrites])
     return d, c, int(n)
 
 

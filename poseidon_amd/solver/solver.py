@@ -97,6 +97,7 @@ class SGDSolver:
                 if self.verbose:
                     print(f"[poseidon] SFB active on: "
                           f"{[l.name for l in marked]}", flush=True)
+        self._mark_dw_overwrite()
 
         self._net_outputs_rows: List[List[float]] = []
         self._net_outputs_cols: List[str] = []
@@ -116,6 +117,39 @@ class SGDSolver:
         # multi-tensor update table (one kernel for ALL params); keyed on
         # tensor identities so restore()/load_weights() invalidate it
         self._mt = None
+        # INNER_PRODUCT layers whose bf16 shadows the last update wrote
+        self._shadow_layers: list = []
+
+    def _mark_dw_overwrite(self) -> None:
+        """Weights with exactly one writer per backward get their gradient
+        WRITTEN into the diff instead of added to a zeroed one (the fused
+        weight tail, docs/architecture.md): fc layers through the dW GEMM's
+        beta 0, single-GPU convs through the deferred unpack. Any number of
+        ranks: the all-reduce reads the finished diff either way. A shared
+        weight keeps accumulating, as does a bare Net without a solver."""
+        net = self.net
+        if ctx().device != "cuda":
+            return
+        users: Dict[int, int] = {}
+        for ps in net.params:
+            users[ps.owner] = users.get(ps.owner, 0) + 1
+        for idx, ps in enumerate(net.params):
+            layer = net.layers[ps.layer_idx]
+            if ps.param_idx != 0 or layer.type_name not in (
+                    "INNER_PRODUCT", "CONVOLUTION"):
+                continue
+            w = ps.blob.data
+            ok = (ps.owner == idx and users[idx] == 1 and ps.lr_mult != 0.0
+                  and net.layer_need_bwd[ps.layer_idx]
+                  and w.is_cuda and w.dtype == torch.float32
+                  and w.is_contiguous()
+                  and not getattr(layer, "sfb_active", False))
+            if layer.type_name == "CONVOLUTION":
+                # only the one-launch unpack at the end of backward can
+                # overwrite; it serves single-bottom convs
+                ok = (ok and getattr(layer, "defer_unpack", False)
+                      and len(net.bottoms[ps.layer_idx]) == 1)
+            layer.dw_overwrite = ok
 
     # ------------------------------------------------------------------
     # hipGraph iteration capture
@@ -175,6 +209,7 @@ class SGDSolver:
     def _graph_body(self) -> torch.Tensor:
         loss = self.forward_backward()
         if not self._mt_update(0.0, lr_dev=self._lr_dev):
+            self.net.invalidate_fc_shadows()  # per-param kernels write none
             for i, ps in enumerate(self.net.params):
                 if ps.owner == i and ps.lr_mult != 0.0:
                     wd = float(self.param.weight_decay or 0.0) * ps.decay_mult
@@ -200,8 +235,27 @@ class SGDSolver:
                  if ps.owner == i and ps.lr_mult != 0.0]
         if not items or not all(ps.blob.has_diff() for _, ps in items):
             return False
-        key = [(id(ps.blob.data), id(ps.blob.diff), id(self.history[i]))
-               for i, ps in items]
+        # fc weights whose owning layer holds a bf16 shadow: the update
+        # writes the shadow too, and the net's repack leaves it out while
+        # the master stays as this kernel left it. Conv shadows are
+        # permuted and stay with the repack; a layer that merely shares the
+        # weight keeps its own shadow there as well.
+        shadows, covered = [], []
+        for _, ps in items:
+            layer = self.net.layers[ps.layer_idx]
+            sh = getattr(layer, "_wk_cache", None)
+            if (ops.fused_weight_tail() and ps.param_idx == 0
+                    and layer.type_name == "INNER_PRODUCT"
+                    and isinstance(sh, torch.Tensor)
+                    and sh.dtype == torch.bfloat16
+                    and sh.numel() == ps.blob.data.numel()):
+                shadows.append(sh)
+                covered.append(layer)
+            else:
+                shadows.append(None)
+        key = [(id(ps.blob.data), id(ps.blob.diff), id(self.history[i]),
+                id(sh) if sh is not None else 0)
+               for (i, ps), sh in zip(items, shadows)]
         if self._mt is None or self._mt[1] != key:
             wd0 = float(self.param.weight_decay or 0.0)
             if self.distributed:
@@ -211,11 +265,20 @@ class SGDSolver:
                 [ps.blob.diff for _, ps in items],
                 [self.history[i] for i, _ in items],
                 [ps.lr_mult for _, ps in items],
-                [wd0 * ps.decay_mult for _, ps in items])
+                [wd0 * ps.decay_mult for _, ps in items],
+                shadows if covered else None)
             self._mt = (mt, key)
         ops.sgd_mt_run(self._mt[0], rate,
                        float(self.param.momentum or 0.0), lr_dev)
+        # recorded after the update: versions as the kernel left them
+        self._shadow_layers = covered
+        self.net.mark_fc_shadows_current(covered)
         return True
+
+    def _refresh_fc_shadows(self) -> None:
+        if self._shadow_layers:
+            self.net._maybe_mt_repack(full=True)
+            self.net.mark_fc_shadows_current(self._shadow_layers)
 
     def _capture_graph(self) -> None:
         dev = ctx().torch_device
@@ -261,6 +324,11 @@ class SGDSolver:
         for t, t0 in saved:
             t.copy_(t0)
         del saved
+        # the shadows the warm-up updates wrote belong to weights that are
+        # gone again: refresh every shadow from the masters now, so that the
+        # capture below records the repack table without the fc shadows and
+        # the first replay reads current ones
+        self._refresh_fc_shadows()
         for l, t0 in counters:
             if l._offset_dev is not None:
                 if t0 is None:
@@ -306,6 +374,12 @@ class SGDSolver:
                 self._stage_inputs()
             self._batch_staged = False
             self._lr_dev.fill_(self.get_learning_rate())
+            # the graph repacks no fc shadow: it relies on the update of the
+            # replay before. A master written since (copy_, load_weights,
+            # restore, a test harness rewinding the weights) shows in its
+            # _version: repack everything once, eagerly, on this stream.
+            if self._shadow_layers and not self.net.fc_shadows_current():
+                self._refresh_fc_shadows()
             self._graph.replay()
             if p.display and self.iter % p.display == 0:
                 last_loss = float(self._graph_loss.item())
@@ -413,6 +487,7 @@ class SGDSolver:
             loss_t = self.forward_backward()
             rate = self.get_learning_rate()
             if not self._mt_update(rate):
+                self.net.invalidate_fc_shadows()
                 for i, ps in enumerate(self.net.params):
                     if ps.owner == i and ps.lr_mult != 0.0:
                         self._apply_update(i, ps, rate)
