@@ -129,7 +129,22 @@ std::atomic<int64_t> g_dgrad_fwd_thresh{128LL << 20};
 // GoogLeNet's 7x7 conv1 gains 1.3% with it on. PS_PACKED_CONV=1 turns it on
 // at import.
 std::atomic<bool> g_packed_conv{false};
+// Row-fused small-channel first layers (ps_rowfused.h, conv_rowfused.hip):
+// bf16 G==1 convs with C % 8 != 0 whose column matrix would reach the
+// threshold run forward and wgrad from staged input rows -- no colT, no
+// im2col. Never in deterministic mode (the wgrad adds floats atomically).
+// Default ON with a 256 MiB threshold, i.e. AlexNet / CaffeNet conv1 (595
+// MB): five of five same-call pairs win on each, by 0.081 / 0.087 ms a step,
+// 5.4x / 3.1x the parent's spread (docs/performance.md item 27). Under the
+// threshold (VGG conv1_1 205 MB, GoogLeNet conv1 154 MB) it measured slower.
+// PS_ROWFUSED_CONV=0/1 sets the switch at import.
+std::atomic<bool> g_rowfused_conv{true};
+std::atomic<int64_t> g_rowfused_thresh{256LL << 20};
 
+void set_rowfused_conv(bool on) { g_rowfused_conv.store(on); }
+bool rowfused_conv() { return g_rowfused_conv.load(); }
+int64_t rowfused_threshold() { return g_rowfused_thresh.load(); }
+void set_rowfused_threshold(int64_t bytes) { g_rowfused_thresh.store(bytes); }
 void set_implicit_gemm(bool on) { g_implicit_gemm.store(on); }
 void set_packed_conv(bool on) { g_packed_conv.store(on); }
 void set_implicit_threshold(int64_t bytes) { g_implicit_thresh.store(bytes); }
@@ -350,19 +365,33 @@ Tensor gemm_at_b(const Tensor& a, const Tensor& b) {
 // packed: PS_PACKED_AUTO asks the global policy; the wgrad passes what its
 // forward actually did (read off the cache slot) instead
 enum { PS_PACKED_OFF = 0, PS_PACKED_ON = 1, PS_PACKED_AUTO = -1 };
+// rowfused likewise: AUTO asks the switch, the threshold and the mode; ON
+// (the forward left the row-fused sentinel) asks only whether the shape can
+// run it; OFF keeps the plan off the path
+enum { PS_ROWFUSED_OFF = 0, PS_ROWFUSED_ON = 1, PS_ROWFUSED_AUTO = -1 };
 
 ConvPlan conv_plan_for(at::IntArrayRef x_shape, int Co, int kh, int kw,
                        int sh, int sw, int ph, int pw, int G, bool bf16,
-                       int packed = PS_PACKED_AUTO) {
+                       int packed = PS_PACKED_AUTO,
+                       int rowfused = PS_ROWFUSED_AUTO) {
   TORCH_CHECK(x_shape.size() == 4 && G > 0 && x_shape[1] % G == 0 &&
               Co % G == 0, "conv channel/group mismatch");
+  const bool rf_auto = rowfused == PS_ROWFUSED_AUTO;
   const ConvPolicy policy = {
       g_implicit_gemm.load(), g_implicit_thresh.load(),
       g_dgrad_fwd_thresh.load(),
-      packed == PS_PACKED_AUTO ? g_packed_conv.load() : packed == PS_PACKED_ON};
-  return ps_conv_plan((int)x_shape[0], (int)x_shape[1], (int)x_shape[2],
-                      (int)x_shape[3], Co, kh, kw, sh, sw, ph, pw, G,
-                      bf16 ? 2 : 4, policy);
+      packed == PS_PACKED_AUTO ? g_packed_conv.load() : packed == PS_PACKED_ON,
+      rf_auto ? g_rowfused_conv.load() : rowfused == PS_ROWFUSED_ON,
+      rf_auto ? g_rowfused_thresh.load() : 0,
+      rf_auto && ps_deterministic() != 0};
+  ConvPlan p = ps_conv_plan((int)x_shape[0], (int)x_shape[1], (int)x_shape[2],
+                            (int)x_shape[3], Co, kh, kw, sh, sw, ph, pw, G,
+                            bf16 ? 2 : 4, policy);
+  // plan time is where the row-fused kernels read the CU count and get their
+  // LDS attribute (once per process), never a launch or a captured region;
+  // without a usable device the plan keeps the column matrix
+  if (p.rowfused && !ps_rowfused_prepare()) p.rowfused = false;
+  return p;
 }
 
 // the plan as Python sees it (Net sizes its persistent wk buffers from it)
@@ -386,6 +415,7 @@ py::dict conv_plan(std::vector<int64_t> x_shape, std::vector<int64_t> w_shape,
   d["Kgw_implicit"] = p.Kgw_implicit; d["dgrad_as_fwd"] = p.dgrad_as_fwd;
   d["packed"] = p.packed; d["pk_W"] = p.pk_W; d["pk_kw"] = p.pk_kw;
   d["pk_Kg"] = p.pk_Kg; d["kw_ld"] = p.kw_ld; d["c_ld"] = p.c_ld;
+  d["rowfused"] = p.rowfused;
   // width of the khwc wgrad scratch
   d["Kgw"] = p.implicit ? p.Kgw_implicit : p.wk_ld;
   return d;
@@ -456,6 +486,30 @@ std::vector<Tensor> conv2d_forward_ex(const Tensor& x, const Tensor& w,
   // the cache slot: colT, the empty 1-D implicit sentinel, or -- 4-D -- the
   // packed xp, which the wgrad gathers from (it never touches x again)
   Tensor colT;
+  if (p.rowfused) {
+    // no column matrix at all: the kernel stages x rows through x's own
+    // strides and keeps wk in LDS. The cache slot is an empty 2-D sentinel
+    // (the implicit one is 1-D, the packed input 4-D).
+    TORCH_CHECK(x.numel() / g.N < (1LL << 31) &&
+                (g.H - 1) * x.stride(2) + (g.W - 1) * x.stride(3) +
+                (g.C - 1) * x.stride(1) < (1LL << 31),
+                "row-fused conv: one image must span < 2^31 elements");
+    TORCH_CHECK(wk.is_contiguous() && ((uintptr_t)wk.data_ptr() & 15) == 0,
+                "row-fused conv: wk must be contiguous and 16 B aligned");
+    const RowFusedTiling t = ps_rowfused_tiling(
+        g.N, g.C, g.H, g.W, Co, g.kh, g.kw, g.sh, g.sw, g.ph, g.pw, p.wk_ld);
+    Tensor y = empty_cl({g.N, Co, g.Ho, g.Wo}, x.options());
+    Tensor bc;
+    const float* bp = nullptr;
+    if (bias.has_value()) {
+      bc = bias->contiguous();
+      bp = bc.data_ptr<float>();
+    }
+    ps_conv_rowfused_fwd(&t, x.data_ptr(), x.stride(0), x.stride(1),
+                         x.stride(2), x.stride(3), wk.data_ptr(), bp,
+                         y.data_ptr(), fuse_relu ? 1 : 0, stream());
+    return {y, at::empty({0, (int64_t)p.ld_col}, x.options()), wkT};
+  }
   if (p.packed) {
     colT = at::empty({g.N, g.H, (int64_t)p.pk_W, PS_PK_C}, x.options());
     ps_pack_pairs_bf16(x.data_ptr(), colT.data_ptr(), g.N, g.C, g.H, g.W,
@@ -589,13 +643,47 @@ Tensor conv2d_backward_weight_acc(const Tensor& x, const Tensor& colT,
   // one between forward and backward must stay harmless
   const bool implicit = colT.numel() == 0 && colT.dim() == 1;
   const bool packed = colT.dim() == 4;
+  // the row-fused forward leaves an empty 2-D slot (a colT has NP rows)
+  const bool rowfused = colT.dim() == 2 && colT.size(0) == 0;
   const ConvPlan p = conv_plan_for(x.sizes(), (int)dw_out.size(0),
                                    (int)dw_out.size(2), (int)dw_out.size(3),
                                    sh, sw, ph, pw, G, is_bf16(dy),
-                                   packed ? PS_PACKED_ON : PS_PACKED_OFF);
+                                   packed ? PS_PACKED_ON : PS_PACKED_OFF,
+                                   rowfused ? PS_ROWFUSED_ON : PS_ROWFUSED_OFF);
   TORCH_CHECK(dw_out.size(1) == p.Cg && dy_cl.size(2) == p.g.Ho &&
               dy_cl.size(3) == p.g.Wo, "conv wgrad: shape mismatch");
   const int Co = p.Co, Cog = p.Cog;
+  if (rowfused) {
+    // dwk[Co][wk_ld] += dy^T @ col from x through its strides: no colT, no
+    // layout copy of x. The kernel adds atomically, which deterministic mode
+    // does not allow -- and there the forward never leaves this sentinel.
+    TORCH_CHECK(p.rowfused && is_bf16(x) && is_bf16(dy),
+                "conv wgrad: row-fused cache slot does not match the plan");
+    TORCH_CHECK(!ps_deterministic(),
+                "conv wgrad: the row-fused wgrad has no deterministic form");
+    const ConvGeom& g = p.g;
+    TORCH_CHECK(x.numel() / g.N < (1LL << 31) &&
+                (g.H - 1) * x.stride(2) + (g.W - 1) * x.stride(3) +
+                (g.C - 1) * x.stride(1) < (1LL << 31),
+                "row-fused conv: one image must span < 2^31 elements");
+    const int Kgw = p.wk_ld;
+    const bool prez =
+        dwk_buf.has_value() && dwk_buf->numel() == (int64_t)Co * Kgw;
+    Tensor dwk = prez ? *dwk_buf
+               : at::empty({Co, (int64_t)Kgw}, dy.options().dtype(at::kFloat));
+    const RowFusedTiling t = ps_rowfused_tiling(
+        g.N, g.C, g.H, g.W, Co, g.kh, g.kw, g.sh, g.sw, g.ph, g.pw, p.wk_ld);
+    ps_conv_rowfused_wgrad(&t, x.data_ptr(), x.stride(0), x.stride(1),
+                           x.stride(2), x.stride(3), dy_cl.data_ptr(),
+                           dwk.data_ptr<float>(), prez ? 1 : 0, stream());
+    if (!skip_unpack)
+      ps_weight_from_khwc_f32(dwk.data_ptr<float>(), dw_out.data_ptr<float>(),
+                              Co, p.Cg, g.kh, g.kw, /*ld=*/Kgw,
+                              /*beta=*/1.0f, p.kw_ld, p.c_ld, stream());
+    if (db_out.has_value() && !skip_db)
+      colsum_into(dy_cl, db_out->data_ptr<float>(), p.NP, Co);
+    return dwk;
+  }
   if (packed) {
     TORCH_CHECK(p.packed && colT.is_contiguous() && is_bf16(colT) &&
                 colT.size(0) == p.g.N && colT.size(1) == p.g.H &&
@@ -1619,6 +1707,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   // one process can run either conv1 path: env overrides, read once here
   if (const char* e = std::getenv("PS_PACKED_CONV"))
     set_packed_conv(std::atoi(e) != 0);
+  m.def("set_rowfused_conv", &set_rowfused_conv);
+  m.def("set_rowfused_threshold", &set_rowfused_threshold);
+  m.def("rowfused_conv", &rowfused_conv);
+  m.def("rowfused_threshold", &rowfused_threshold);
+  // tests only: cap on the row-fused kernels' persistent grid (0 = auto)
+  m.def("set_rowfused_blocks", &ps_rowfused_set_blocks);
+  if (const char* e = std::getenv("PS_ROWFUSED_CONV"))
+    set_rowfused_conv(std::atoi(e) != 0);
   m.def("set_dgrad_fwd_threshold", &set_dgrad_fwd_threshold);
   m.def("concat_channels", &concat_channels);
   m.def("slice_channels", &slice_channels);

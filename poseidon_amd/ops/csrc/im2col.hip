@@ -144,6 +144,12 @@ __global__ void pack_pairs_k(const __bf16* __restrict__ x,
 // AlexNet/CaffeNet/GoogLeNet conv1, VGG conv1_1, CIFAR, LeNet. With it on,
 // the even-stride bf16 ones (AlexNet/CaffeNet/GoogLeNet conv1) leave for
 // the packed plan; stride-1 and fp32 layers stay here.
+// With the row-fused switch on (the default), bf16 layers whose column
+// matrix reaches its threshold (256 MiB: AlexNet / CaffeNet conv1) leave for
+// conv_rowfused.hip, which runs their forward and wgrad from the staged
+// rows without a column matrix. Every fp32 first layer, bf16 ones under the
+// threshold (VGG conv1_1, GoogLeNet conv1, CIFAR, LeNet) and everything in
+// deterministic mode stay here.
 // The rowrun kernel above issues unaligned 16 B ops on 66 B
 // runs (every op splits into two requests) and re-reads overlapping
 // windows from HBM; here a block stages the kh input rows of one (n, oh)

@@ -207,6 +207,23 @@ void ps_data_transform_f32(const uint8_t*, const int*, const float*, float*,
 void ps_data_transform_bf16(const uint8_t*, const int*, const float*, void*,
                             const TransformGeom*, hipStream_t);
 
+// conv_rowfused.hip: row-fused first layer (ps_rowfused.h), bf16 only. x is
+// read through its element strides (sn, sc, sh, sw); wk is the khwc shadow
+// [Co][Kpad]; y / dy are NHWC rows; dwk is f32 [Co][Kpad], added to
+// atomically (cleared first unless prezeroed).
+void ps_conv_rowfused_fwd(const RowFusedTiling*, const void* x, int64_t sn,
+                          int64_t sc, int64_t sh, int64_t sw, const void* wk,
+                          const float* bias, void* y, int relu, hipStream_t);
+void ps_conv_rowfused_wgrad(const RowFusedTiling*, const void* x, int64_t sn,
+                            int64_t sc, int64_t sh, int64_t sw,
+                            const void* dy, float* dwk, int prezeroed,
+                            hipStream_t);
+// once per process, when a plan comes out row-fused: reads the CU count and
+// sets the kernels' LDS attribute; 0 = no usable device
+int ps_rowfused_prepare();
+// tests only: cap on the persistent grid (0 = one block per CU)
+void ps_rowfused_set_blocks(int n);
+
 // im2col.hip
 void ps_chan_concat4_f32(float*, void* const*, const int*, int, int, int64_t,
                          int, int, const void* const*, hipStream_t);

@@ -5,6 +5,8 @@
 #pragma once
 #include <cstdint>
 
+#include "ps_rowfused.h"
+
 #if defined(__HIPCC__)
 #define PS_HD __host__ __device__
 #else
@@ -46,6 +48,12 @@ struct ConvPolicy {
   int64_t implicit_bytes;   // colT above this goes implicit per layer
   int64_t dgrad_fwd_bytes;  // dcolT above this runs dgrad as a forward conv
   bool packed;              // packed small-channel first-layer switch
+  // row-fused small-channel first layers (ps_rowfused.h): switch, the colT
+  // size above which a layer takes the path, and deterministic mode, which
+  // keeps it off (its wgrad adds floats atomically)
+  bool rowfused;
+  int64_t rowfused_bytes;
+  bool deterministic;
 };
 
 // Packed first-layer layout (G==1, C <= 4, even sw): x is copied once into
@@ -109,6 +117,10 @@ struct ConvPlan {
   int pk_kw;        // kw': taps per row in chunks, ceil(kw / 2)
   int pk_Kg;        // kh * pk_kw * 8
   int kw_ld, c_ld;  // khwc tap-row width and channel slots (ps_khwc_col)
+  // row-fused first layer: forward and wgrad build their operands from
+  // staged input rows (conv_rowfused.hip); no column matrix. The layouts
+  // (ld_col, wk_ld, khwc order) are the materialized path's.
+  bool rowfused;
 };
 
 inline ConvPlan ps_conv_plan(int N, int C, int H, int W, int Co, int kh,
@@ -146,6 +158,14 @@ inline ConvPlan ps_conv_plan(int N, int C, int H, int W, int Co, int kh,
     p.wk_ld = (p.pk_Kg + 63) & ~63;
     p.kpad = true;  // unused slots / phantom taps / pad columns stay zero
   }
+  // the shapes im2col_rowstage_k takes, once the colT they would write is
+  // big enough to matter and both kernels' LDS images fit
+  p.rowfused = policy.rowfused && !policy.deterministic && elem_bytes == 2 &&
+               G == 1 && C % p.vec != 0 && !p.is_1x1 && !p.packed &&
+               !p.implicit && p.g.Ho > 0 && p.g.Wo > 0 &&
+               p.NP * p.ld_col * elem_bytes >= policy.rowfused_bytes &&
+               ps_rowfused_tiling(N, C, H, W, Co, kh, kw, sh, sw, ph, pw,
+                                  p.wk_ld).ok;
   // worth it only when the dcolT it eliminates is substantial (small
   // inception dgrads measured faster on the materialized NT + col2im)
   p.dgrad_as_fwd = sh == 1 && sw == 1 && !p.is_1x1 && p.Cog % p.vec == 0 &&

@@ -72,6 +72,43 @@ def set_packed_conv(on: bool) -> None:
     _conv_policy_epoch += 1
 
 
+ROWFUSED_THRESHOLD_DEFAULT = 256 << 20
+
+
+def set_rowfused_conv(on: bool) -> None:
+    """Toggle the row-fused first-layer path (bf16, G==1, C % 8 != 0, not
+    1x1): forward and wgrad build their MFMA operands from input rows staged
+    in LDS, and no column matrix is written or read. Default on for layers
+    whose column matrix reaches set_rowfused_threshold (AlexNet / CaffeNet
+    conv1, docs/performance.md item 27); never taken in deterministic mode. The khwc weight layout is the materialized path's,
+    so no persistent buffer changes. The environment variable
+    PS_ROWFUSED_CONV=0/1 sets it at import."""
+    if ext_available():
+        _ext().set_rowfused_conv(bool(on))
+
+
+def rowfused_conv() -> bool:
+    return bool(_ext().rowfused_conv()) if ext_available() else False
+
+
+def set_rowfused_threshold(bytes_: int) -> None:
+    """Column-matrix size from which a first layer goes row-fused."""
+    if ext_available():
+        _ext().set_rowfused_threshold(int(bytes_))
+
+
+def rowfused_threshold() -> int:
+    return (int(_ext().rowfused_threshold()) if ext_available()
+            else ROWFUSED_THRESHOLD_DEFAULT)
+
+
+def _set_rowfused_blocks(n: int) -> None:
+    """Tests only: cap on the row-fused kernels' persistent grid (0 = one
+    block per CU), so that a small case walks several tiles per block."""
+    if ext_available():
+        _ext().set_rowfused_blocks(int(n))
+
+
 def conv_policy_epoch() -> int:
     return _conv_policy_epoch
 

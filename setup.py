@@ -25,6 +25,7 @@ sources = [
         "softmax.hip",
         "sgd.hip",
         "im2col.hip",
+        "conv_rowfused.hip",
         "transform.hip",
     ]
 ]
