@@ -127,6 +127,12 @@ class Net:
         self._ms_pool = None
         self._fwd_ev = None
         self._bwd_ev = None
+        # solver debug_info (core/debug_info.py): off unless asked for; the
+        # slots are laid out at first use. A distributed solver defers the
+        # param-diff statistics until its all-reduce is done.
+        self._dbg = None
+        self._dbg_on = False
+        self._dbg_defer_param_diffs = False
 
         self._build()
         self._build_stream_schedule()
@@ -454,6 +460,8 @@ class Net:
         (which already removes the launch gaps these streams target) is
         the winning configuration today."""
         import os
+        if self._dbg_on:
+            return False  # debug passes run the serial schedule
         return (self._ms_nstreams > 1 and ctx().device == "cuda"
                 and torch.cuda.is_available()
                 and os.environ.get("PS_MULTI_STREAM", "0") == "1")
@@ -721,15 +729,46 @@ class Net:
         self._fc_marks = None
         ops.repack_mt_run(self._repack_mt)
 
+    # -- debug_info ------------------------------------------------------
+    def set_debug_info(self, on: bool) -> None:
+        """Per-layer blob statistics for the passes that follow (reference
+        Net::set_debug_info). Read them back with debug_records()."""
+        self._dbg_on = bool(on)
+        if self._dbg_on and self._dbg is None:
+            from .debug_info import DebugInfo
+            self._dbg = DebugInfo(self)
+
+    @property
+    def debug_info(self) -> bool:
+        return self._dbg_on
+
+    def debug_records(self) -> List[dict]:
+        """Records of the last pass run with debug_info on: one device-to-
+        host copy of the statistics buffer."""
+        return self._dbg.records() if self._dbg is not None else []
+
+    def debug_param_diffs(self) -> None:
+        """Take the param-diff statistics now (the distributed solver, after
+        its all-reduce; a local backward() does it itself)."""
+        if self._dbg_on:
+            self._dbg.param_diffs()
+
     def forward(self, start: int = 0, end: Optional[int] = None) -> float:
         end = len(self.layers) if end is None else end
         self._maybe_mt_repack()
+        dbg = self._dbg if self._dbg_on else None
+        if dbg is not None:
+            dbg.begin()
         loss = 0.0
         for i in range(start, end):
             self.layers[i].forward(self.bottoms[i], self.tops[i])
+            if dbg is not None:
+                dbg.tops(i)
             for (li, ti, w) in self._loss_tops:
                 if li == i:
                     loss += w * float(self.tops[i][ti].data.sum().item())
+        if dbg is not None:
+            dbg.end_forward()
         return loss
 
     def forward_async(self) -> torch.Tensor:
@@ -748,11 +787,18 @@ class Net:
         layers = self.layers
         bottoms = self.bottoms
         tops = self.tops
+        dbg = self._dbg if self._dbg_on else None
+        if dbg is not None:
+            dbg.begin()
         for i in range(len(layers)):
             layers[i].forward(bottoms[i], tops[i])
+            if dbg is not None:
+                dbg.tops(i)
             if i in marks:
                 for (ti, w) in marks[i]:
                     loss = loss + w * tops[i][ti].data.sum().to(torch.float32)
+        if dbg is not None:
+            dbg.end_forward()
         return loss
 
     def _forward_ms(self) -> None:
@@ -800,14 +846,20 @@ class Net:
             self._backward_ms(post_layer_cb)
             self._flush_deferred_unpacks()
             return
+        dbg = self._dbg if self._dbg_on else None
         for i in range(len(self.layers) - 1, -1, -1):
             if not self.layer_need_bwd[i]:
                 continue
             self.layers[i].backward(self.tops[i], self.bottom_need_bwd[i],
                                     self.bottoms[i])
+            if dbg is not None:
+                dbg.bottoms(i)
             if post_layer_cb is not None and self.layers[i].blobs:
                 post_layer_cb(i, self.layers[i])
         self._flush_deferred_unpacks()
+        # param diffs are final only here (deferred unpacks, batched colsum)
+        if dbg is not None and not self._dbg_defer_param_diffs:
+            dbg.param_diffs()
 
     def _backward_ms(self, post_layer_cb) -> None:
         """Backward mirror of _forward_ms: layer i runs on its forward

@@ -1478,6 +1478,93 @@ void zero_mt_run(const Tensor& desc_dev, const Tensor& chunk_dev,
              stream());
 }
 
+// Blob statistics (stats.hip). The three buffers a caller keeps: stats
+// [slots][4] f32 (StatsRec), scratch [slots][STATS_MAX_BLOCKS][4] f32, nblk
+// [slots] i32. A tensor is read as its flat storage, which any
+// non-overlapping dense layout allows; anything else raises (no copy).
+std::vector<int64_t> blob_stats_plan(int64_t count, int64_t itemsize) {
+  TORCH_CHECK(count >= 0 && (itemsize == 2 || itemsize == 4),
+              "blob_stats_plan: bf16 or fp32 elements");
+  const ps::StatsPlan p = ps::stats_plan(count, (int)itemsize);
+  return {p.blocks, p.chain};
+}
+int64_t blob_stats_reduce_depth(int64_t blocks, int64_t itemsize) {
+  return ps::stats_reduce_depth((int)blocks, (int)itemsize);
+}
+int64_t blob_stats_max_blocks() { return ps::STATS_MAX_BLOCKS; }
+
+void check_stats_input(const Tensor& t) {
+  check_float_like(t, "blob_stats");
+  TORCH_CHECK(t.is_non_overlapping_and_dense(),
+              "blob_stats: tensor must be non-overlapping and dense");
+  TORCH_CHECK(t.numel() < (int64_t)1 << 32, "blob_stats: tensor too large");
+}
+void check_stats_buffers(const Tensor& scratch, const Tensor& nblk,
+                         int64_t slot_end) {
+  TORCH_CHECK(scratch.is_cuda() && scratch.is_contiguous() &&
+              scratch.scalar_type() == at::kFloat &&
+              nblk.is_cuda() && nblk.is_contiguous() &&
+              nblk.scalar_type() == at::kInt,
+              "blob_stats: scratch must be f32 and nblk i32, on the device");
+  TORCH_CHECK(slot_end <= nblk.numel() &&
+              scratch.numel() >= nblk.numel() * ps::STATS_MAX_BLOCKS * 4,
+              "blob_stats: slot out of range");
+}
+
+void blob_stats(const Tensor& t, Tensor scratch, Tensor nblk, int64_t slot) {
+  check_stats_input(t);
+  TORCH_CHECK(slot >= 0, "blob_stats: negative slot");
+  check_stats_buffers(scratch, nblk, slot + 1);
+  ps_blob_stats(t.data_ptr(), t.numel(), is_bf16(t) ? 1 : 0, (int)slot,
+                scratch.data_ptr(), nblk.data_ptr<int>(), stream());
+}
+
+std::vector<Tensor> blob_stats_mt_prepare(std::vector<Tensor> ts,
+                                          std::vector<int64_t> slots) {
+  TORCH_CHECK(!ts.empty() && ts.size() == slots.size(),
+              "blob_stats_mt_prepare: one slot per tensor");
+  std::vector<ps::StatsDesc> descs(ts.size());
+  int64_t max_slot = 0;
+  for (size_t t = 0; t < ts.size(); ++t) {
+    check_stats_input(ts[t]);
+    TORCH_CHECK(slots[t] >= 0 && ts[t].numel() > 0,
+                "blob_stats_mt_prepare: empty tensor or negative slot");
+    const int bf = is_bf16(ts[t]) ? 1 : 0;
+    descs[t] = {ts[t].data_ptr(), ts[t].numel(), (int)slots[t],
+                ps::stats_plan(ts[t].numel(), bf ? 2 : 4).blocks, bf, 0};
+    max_slot = std::max(max_slot, slots[t]);
+  }
+  auto mt = mt_tables(descs, ts[0], [](const ps::StatsDesc& d) {
+    return std::pair<int64_t, int64_t>(d.blocks, 1);
+  });
+  mt.push_back(at::scalar_tensor(max_slot));
+  return mt;
+}
+
+void blob_stats_mt_run(const Tensor& desc_dev, const Tensor& chunk_dev,
+                       int64_t nchunks, int64_t max_slot, Tensor scratch,
+                       Tensor nblk) {
+  check_stats_buffers(scratch, nblk, max_slot + 1);
+  ps_blob_stats_mt(desc_dev.data_ptr(), chunk_dev.data_ptr(), (int)nchunks,
+                   scratch.data_ptr(), nblk.data_ptr<int>(), stream());
+}
+
+void blob_stats_finalize(Tensor stats, const Tensor& scratch,
+                         const Tensor& nblk, int64_t slot0, int64_t nslots) {
+  TORCH_CHECK(slot0 >= 0 && nslots >= 0, "blob_stats_finalize: bad range");
+  check_stats_buffers(scratch, nblk, slot0 + nslots);
+  TORCH_CHECK(stats.is_cuda() && stats.is_contiguous() &&
+              stats.scalar_type() == at::kFloat &&
+              stats.numel() >= nblk.numel() * 4,
+              "blob_stats_finalize: stats must be f32 [slots][4]");
+  ps_blob_stats_finalize(scratch.data_ptr(), nblk.data_ptr<int>(),
+                         stats.data_ptr(), (int)slot0, (int)nslots, stream());
+}
+
+int64_t blob_stats_launches(bool reset) {
+  return ps_blob_stats_launches(reset ? 1 : 0);
+}
+
 // one launch sums every deferred conv bias gradient: descs keyed on the
 // (now identity-stable) activation-grad buffers. Chunk.off = start row.
 std::vector<Tensor> colsum_mt_prepare(std::vector<Tensor> dys,
@@ -1757,6 +1844,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("zero_mt_prepare", &zero_mt_prepare);
   m.def("zero_mt_run", &zero_mt_run);
   m.def("repack_mt_prepare", &repack_mt_prepare);
+  m.def("blob_stats_plan", &blob_stats_plan);
+  m.def("blob_stats_reduce_depth", &blob_stats_reduce_depth);
+  m.def("blob_stats_max_blocks", &blob_stats_max_blocks);
+  m.def("blob_stats", &blob_stats);
+  m.def("blob_stats_mt_prepare", &blob_stats_mt_prepare);
+  m.def("blob_stats_mt_run", &blob_stats_mt_run);
+  m.def("blob_stats_finalize", &blob_stats_finalize);
+  m.def("blob_stats_launches", &blob_stats_launches);
   m.def("colsum_mt_prepare", &colsum_mt_prepare);
   m.def("colsum_mt_run", &colsum_mt_run);
   m.def("colsum_acc", &colsum_acc);

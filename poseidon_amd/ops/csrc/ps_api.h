@@ -5,6 +5,7 @@
 
 #include "ps_conv_plan.h"  // ConvGeom, GatherDesc, ConvPlan
 #include "ps_gemm_plan.h"  // GemmPlan, TrTune
+#include "ps_stats_plan.h"  // StatsPlan, StatsRec
 #include "ps_transform.h"  // TransformGeom, PS_MEAN_*
 
 struct GemmArgs {
@@ -199,6 +200,19 @@ void ps_repack_mt(const void* descs, const void* chunks, int nchunks,
                   hipStream_t);
 void ps_unpack_mt(const void* descs, const void* chunks, int nchunks,
                   hipStream_t);
+
+// stats.hip: blob statistics for debug_info (ps_stats_plan.h). scratch is
+// [slots][STATS_MAX_BLOCKS] StatsRec partials, nblk [slots] the block count
+// each slot was last launched with, stats [slots] StatsRec.
+void ps_blob_stats(const void* p, int64_t n, int bf16, int slot,
+                   void* scratch, int* nblk, hipStream_t);
+// (StatsDesc table, MTChunk table with off = block index, chunks)
+void ps_blob_stats_mt(const void* descs, const void* chunks, int nchunks,
+                      void* scratch, int* nblk, hipStream_t);
+void ps_blob_stats_finalize(const void* scratch, const int* nblk, void* stats,
+                            int slot0, int nslots, hipStream_t);
+// host-side count of the three launches above
+int64_t ps_blob_stats_launches(int reset);
 
 // transform.hip: (raw uint8 [N,C,H,W], params int32 [N,3], mean | null, out
 // [N,C,Ho,Wo], geom). out must be aligned to 8 of its elements.

@@ -56,6 +56,17 @@ struct MTUnpackDesc {
                      // that nobody zeroed)
 };
 
+// blob statistics (stats.hip); its chunks count BLOCKS of the tensor's plan
+// (MTChunk.off = block index within the tensor)
+struct StatsDesc {
+  const void* p;  // dense storage, bf16 or fp32, element-aligned only
+  int64_t n;
+  int slot;
+  int blocks;     // ps_stats_plan.h
+  int bf16;
+  int pad;
+};
+
 // bias colsum; its chunks count ROWS (ColsumChunk.off = start row)
 struct ColsumDesc {
   const void* dy;

@@ -818,6 +818,147 @@ def zero_mt_run(mt) -> None:
     _ext().zero_mt_run(desc, chunk, nchunks)
 
 
+# -- blob statistics (solver debug_info) -------------------------------------
+# Per tensor: sum of |x| (NaN / Inf propagate), largest finite |x|, number of
+# NaN / Inf elements. On the GPU one streaming pass per tensor stores block
+# partials to a persistent scratch and blob_stats_finalize sums them in a
+# fixed order (stats.hip): no float atomics, no host sync, capturable. The
+# CPU path computes the same three numbers with torch, the sum in float64.
+
+class BlobStatsBuffer:
+    """The persistent buffers of nslots statistics records. records() is the
+    one device-to-host copy."""
+
+    def __init__(self, nslots: int, device) -> None:
+        device = torch.device(device)
+        self.nslots = int(nslots)
+        self.is_cuda = device.type == "cuda"
+        if self.is_cuda:
+            mb = int(_ext().blob_stats_max_blocks())
+            self.stats = torch.zeros(self.nslots, 4, dtype=torch.float32,
+                                     device=device)
+            self.scratch = torch.zeros(self.nslots, mb, 4,
+                                       dtype=torch.float32, device=device)
+            self.nblk = torch.zeros(self.nslots, dtype=torch.int32,
+                                    device=device)
+        else:
+            self.stats = torch.zeros(self.nslots, 4, dtype=torch.float64)
+            self.scratch = self.nblk = None
+
+    def records(self):
+        """[(asum, maxabs, nonfinite)] per slot, as Python numbers."""
+        if self.is_cuda:
+            host = self.stats.cpu()
+            nf = host.view(torch.int32)[:, 2].tolist()
+        else:
+            host = self.stats
+            nf = [int(v) for v in host[:, 2].tolist()]
+        return list(zip(host[:, 0].tolist(), host[:, 1].tolist(), nf))
+
+
+def _stats_dense(t: torch.Tensor) -> bool:
+    """Non-overlapping and dense: some order of the dimensions walks the
+    storage without gaps."""
+    dims = sorted((st, sz) for sz, st in zip(t.shape, t.stride()) if sz != 1)
+    expect = 1
+    for st, sz in dims:
+        if st != expect:
+            return False
+        expect *= sz
+    return True
+
+
+def _stats_check(t: torch.Tensor) -> None:
+    if t.dtype not in (torch.float32, torch.bfloat16):
+        raise TypeError("blob_stats: expected float32 or bfloat16")
+    if not _stats_dense(t):
+        raise ValueError("blob_stats: tensor must be non-overlapping and "
+                         "dense (it is read in place, never copied)")
+
+
+def _stats_cpu(t: torch.Tensor, out: BlobStatsBuffer, slot: int) -> None:
+    a = t.detach().abs()
+    fin = torch.isfinite(a)
+    nf = int(a.numel() - int(fin.sum()))
+    finite = a[fin]
+    out.stats[slot, 0] = a.double().sum()
+    out.stats[slot, 1] = float(finite.max()) if finite.numel() else 0.0
+    out.stats[slot, 2] = nf
+    out.stats[slot, 3] = 0.0
+
+
+def blob_stats_plan(count: int, itemsize: int) -> Tuple[int, int]:
+    """(blocks, longest serial add chain per accumulator) of the GPU pass
+    over count elements of itemsize bytes."""
+    blocks, chain = _ext().blob_stats_plan(int(count), int(itemsize))
+    return int(blocks), int(chain)
+
+
+def blob_stats_reduce_depth(blocks: int, itemsize: int) -> int:
+    """Float adds between one accumulator and the record (vector, unroll,
+    lane, wave and partial sums) for a launch of that many blocks."""
+    return int(_ext().blob_stats_reduce_depth(int(blocks), int(itemsize)))
+
+
+def blob_stats(t: torch.Tensor, out: BlobStatsBuffer, slot: int) -> None:
+    """Statistics of one tensor into slot (GPU: its partials; the record is
+    there after blob_stats_finalize). Everything goes as kernel arguments,
+    so the launch is safe under graph capture for any tensor."""
+    _stats_check(t)
+    if not 0 <= slot < out.nslots:
+        raise IndexError("blob_stats: slot out of range")
+    if t.numel() == 0:
+        return
+    if t.is_cuda:
+        _ext().blob_stats(t, out.scratch, out.nblk, int(slot))
+    else:
+        _stats_cpu(t, out, slot)
+
+
+def blob_stats_mt_prepare(tensors, slots):
+    """One table for a set of identity-stable tensors (all param diffs, all
+    histories): blob_stats_mt_run covers them in a single launch. Rebuild it
+    when a tensor's identity changes."""
+    tensors, slots = list(tensors), [int(s) for s in slots]
+    for t in tensors:
+        _stats_check(t)
+    if tensors and tensors[0].is_cuda:
+        d, c, n, ms = _ext().blob_stats_mt_prepare(tensors, slots)
+        return d, c, int(n), int(ms), tensors
+    return None, None, 0, max(slots, default=0), list(zip(tensors, slots))
+
+
+def blob_stats_mt_run(mt, out: BlobStatsBuffer) -> None:
+    d, c, n, ms, held = mt
+    if ms >= out.nslots:
+        raise IndexError("blob_stats_mt_run: slot out of range")
+    if d is not None:
+        _ext().blob_stats_mt_run(d, c, n, ms, out.scratch, out.nblk)
+        return
+    for t, slot in held:
+        _stats_cpu(t, out, slot)
+
+
+def blob_stats_finalize(out: BlobStatsBuffer, slot0: int = 0,
+                        nslots: Optional[int] = None) -> None:
+    """Sum the partials of slots [slot0, slot0 + nslots) into their records:
+    once per phase, after the phase's launches. Nothing to do on the CPU."""
+    nslots = out.nslots - slot0 if nslots is None else nslots
+    if slot0 < 0 or nslots < 0 or slot0 + nslots > out.nslots:
+        raise IndexError("blob_stats_finalize: slot range out of bounds")
+    if out.is_cuda and nslots:
+        _ext().blob_stats_finalize(out.stats, out.scratch, out.nblk,
+                                   int(slot0), int(nslots))
+
+
+def blob_stats_launches(reset: bool = False) -> int:
+    """Launches so far of the statistics kernels (single, multi-tensor and
+    finalize): a host-side counter, like float_atomic_launches."""
+    if not ext_available():
+        return 0
+    return int(_ext().blob_stats_launches(bool(reset)))
+
+
 def nesterov_update(w, grad, hist, local_rate: float, momentum: float,
                     decay: float) -> None:
     """update = (1+mu)*h_new - mu*h_old (solver.cpp:1013-1120)."""

@@ -98,6 +98,11 @@ class SGDSolver:
                     print(f"[poseidon] SFB active on: "
                           f"{[l.name for l in marked]}", flush=True)
         self._mark_dw_overwrite()
+        # debug_info: records of the last display iteration. The train net
+        # only -- test nets never report, as in the reference. Distributed,
+        # the param diffs are read after the all-reduce (forward_backward).
+        self.debug_records: List[dict] = []
+        self.net._dbg_defer_param_diffs = self.reducer is not None
 
         self._net_outputs_rows: List[List[float]] = []
         self._net_outputs_cols: List[str] = []
@@ -208,6 +213,7 @@ class SGDSolver:
 
     def _graph_body(self) -> torch.Tensor:
         loss = self.forward_backward()
+        saved = self._debug_pre_update()
         if not self._mt_update(0.0, lr_dev=self._lr_dev):
             self.net.invalidate_fc_shadows()  # per-param kernels write none
             for i, ps in enumerate(self.net.params):
@@ -219,7 +225,41 @@ class SGDSolver:
                                    self.history[i], ps.lr_mult,
                                    float(self.param.momentum or 0.0),
                                    wd, lr_dev=self._lr_dev)
+        self._debug_post_update(saved)
         return loss
+
+    # -- debug_info: the [Update] statistics -----------------------------
+    def _debug_pre_update(self):
+        """Param data before the update. Returns None when debug_info is off
+        for this pass; else the state _debug_post_update needs: nothing for
+        SGD (its update value is the history the kernel leaves), clones of
+        the params for solvers that never store theirs."""
+        if not self.net.debug_info:
+            return None
+        self.net._dbg.update_data()
+        if type(self) is SGDSolver:
+            return {}
+        return {i: self.net.params[i].blob.data.clone() for i in self.history}
+
+    def _debug_post_update(self, saved) -> None:
+        if saved is None:
+            return
+        if saved:
+            values = {i: w0.sub_(self.net.params[i].blob.data)
+                      for i, w0 in saved.items()}
+            self.net._dbg.update_values(values, stable=False)
+        else:
+            self.net._dbg.update_values(dict(self.history), stable=True)
+
+    def _print_debug_info(self) -> None:
+        """The reference's debug_info lines for the pass just run, kept in
+        debug_records; printed by the root rank right before the display
+        line."""
+        from ..core.debug_info import format_records
+        self.debug_records = self.net.debug_records()
+        if self.verbose:
+            for line in format_records(self.debug_records):
+                print(line, flush=True)
 
     # -- multi-tensor update: one sgd_mt kernel covers every param ------
     def _mt_update(self, rate: float, lr_dev=None) -> bool:
@@ -284,6 +324,10 @@ class SGDSolver:
         dev = ctx().torch_device
         self._lr_dev = torch.zeros(1, dtype=torch.float32, device=dev)
         self._lr_dev.fill_(self.get_learning_rate())
+        # debug_info: the statistics launches are part of the one graph, so
+        # every replay refreshes the buffer and display iterations only copy
+        # it back. On from the warm-up, which builds their tables.
+        self.net.set_debug_info(bool(self.param.debug_info))
         # The warm-up passes below are full updates at the current rate that
         # no iteration counts: keep what they change and put it back IN
         # PLACE afterwards (the graph and the multi-tensor tables hold these
@@ -383,6 +427,8 @@ class SGDSolver:
             self._graph.replay()
             if p.display and self.iter % p.display == 0:
                 last_loss = float(self._graph_loss.item())
+                if self.net.debug_info:
+                    self._print_debug_info()
                 self._display(last_loss, self.get_learning_rate())
             self.iter += 1
             iters -= 1
@@ -460,6 +506,8 @@ class SGDSolver:
             self.reducer.wait()
             if self.sfb is not None:
                 self.sfb.finish()
+            # the gradient the update consumes
+            net.debug_param_diffs()
         else:
             net.backward()
         return loss
@@ -484,15 +532,21 @@ class SGDSolver:
             if (p.test_interval and self.iter % p.test_interval == 0
                     and (self.iter > 0 or bool(p.test_initialization))):
                 self.test_all()
+            display = bool(p.display) and self.iter % p.display == 0
+            self.net.set_debug_info(display and bool(p.debug_info))
             loss_t = self.forward_backward()
             rate = self.get_learning_rate()
+            saved = self._debug_pre_update()
             if not self._mt_update(rate):
                 self.net.invalidate_fc_shadows()
                 for i, ps in enumerate(self.net.params):
                     if ps.owner == i and ps.lr_mult != 0.0:
                         self._apply_update(i, ps, rate)
-            if p.display and self.iter % p.display == 0:
+            self._debug_post_update(saved)
+            if display:
                 last_loss = float(loss_t.item())
+                if self.net.debug_info:
+                    self._print_debug_info()
                 self._display(last_loss, rate)
             self.iter += 1
             iters -= 1

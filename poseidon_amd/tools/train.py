@@ -51,6 +51,12 @@ def main(argv=None):
                          "(DB-backed data layers need --device-transform); "
                          "falls back to eager where the net cannot be "
                          "captured")
+    ap.add_argument("--debug-info", action="store_true",
+                    help="force the solver's debug_info on: at every display "
+                         "iteration print the mean |x| of each layer's tops, "
+                         "bottom and param diffs and each param's data and "
+                         "update, plus a [Watch] line per blob holding NaN "
+                         "or Inf (train net only)")
     args = ap.parse_args(argv)
 
     import poseidon_amd as pa
@@ -58,6 +64,8 @@ def main(argv=None):
     from poseidon_amd.solver.solver import get_solver
 
     solver_param = read_proto_text(args.solver, "SolverParameter")
+    if args.debug_info:
+        solver_param.debug_info = True
     use_gpu = torch.cuda.is_available() and not args.cpu \
         and solver_param.enum_name("solver_mode") == "GPU"
     cd = torch.bfloat16 if (args.dtype == "bf16" and use_gpu) else torch.float32

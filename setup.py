@@ -27,6 +27,7 @@ sources = [
         "im2col.hip",
         "conv_rowfused.hip",
         "transform.hip",
+        "stats.hip",
     ]
 ]
 
