@@ -370,6 +370,18 @@ enum { PS_PACKED_OFF = 0, PS_PACKED_ON = 1, PS_PACKED_AUTO = -1 };
 // run it; OFF keeps the plan off the path
 enum { PS_ROWFUSED_OFF = 0, PS_ROWFUSED_ON = 1, PS_ROWFUSED_AUTO = -1 };
 
+// elements from x's first to its last, inclusive: what the row-fused staging
+// may read (ps_rowfused.h, RowFusedX::span)
+int64_t rowfused_span(const Tensor& x) {
+  int64_t span = 1;
+  for (int64_t d = 0; d < x.dim(); ++d) {
+    TORCH_CHECK(x.size(d) > 0 && x.stride(d) >= 0,
+                "row-fused conv: empty or negatively strided x");
+    span += (x.size(d) - 1) * x.stride(d);
+  }
+  return span;
+}
+
 ConvPlan conv_plan_for(at::IntArrayRef x_shape, int Co, int kh, int kw,
                        int sh, int sw, int ph, int pw, int G, bool bf16,
                        int packed = PS_PACKED_AUTO,
@@ -506,8 +518,9 @@ std::vector<Tensor> conv2d_forward_ex(const Tensor& x, const Tensor& w,
       bp = bc.data_ptr<float>();
     }
     ps_conv_rowfused_fwd(&t, x.data_ptr(), x.stride(0), x.stride(1),
-                         x.stride(2), x.stride(3), wk.data_ptr(), bp,
-                         y.data_ptr(), fuse_relu ? 1 : 0, stream());
+                         x.stride(2), x.stride(3), rowfused_span(x),
+                         wk.data_ptr(), bp, y.data_ptr(), fuse_relu ? 1 : 0,
+                         stream());
     return {y, at::empty({0, (int64_t)p.ld_col}, x.options()), wkT};
   }
   if (p.packed) {
@@ -674,8 +687,9 @@ Tensor conv2d_backward_weight_acc(const Tensor& x, const Tensor& colT,
     const RowFusedTiling t = ps_rowfused_tiling(
         g.N, g.C, g.H, g.W, Co, g.kh, g.kw, g.sh, g.sw, g.ph, g.pw, p.wk_ld);
     ps_conv_rowfused_wgrad(&t, x.data_ptr(), x.stride(0), x.stride(1),
-                           x.stride(2), x.stride(3), dy_cl.data_ptr(),
-                           dwk.data_ptr<float>(), prez ? 1 : 0, stream());
+                           x.stride(2), x.stride(3), rowfused_span(x),
+                           dy_cl.data_ptr(), dwk.data_ptr<float>(),
+                           prez ? 1 : 0, stream());
     if (!skip_unpack)
       ps_weight_from_khwc_f32(dwk.data_ptr<float>(), dw_out.data_ptr<float>(),
                               Co, p.Cg, g.kh, g.kw, /*ld=*/Kgw,

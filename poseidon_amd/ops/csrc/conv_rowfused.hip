@@ -45,11 +45,10 @@ constexpr int RF_STAGERS = 256;  // the forward's waves 4-7
 typedef __attribute__((ext_vector_type(4))) __bf16 rf_bf16x4;
 typedef __attribute__((ext_vector_type(4))) int rf_i32x4;
 
-// x strides in elements
+// x: its first element and how to walk it (strides in elements, span)
 struct RfX {
   const __bf16* x;
-  int64_t sn;      // image stride
-  int sc, sh, sw;  // strides inside one image
+  RowFusedX g;
 };
 
 // one staged bf16 at byte offset pbase + koff of the image (zero header for
@@ -60,57 +59,105 @@ __device__ inline __bf16 rf_read(const char* img, int pbase, int koff) {
 
 // A tile's input window, global -> registers -> LDS, in two halves so that a
 // caller can leave the loads in flight across other work. The image is
-// channel-planar (ps_rowfused.h): its 16 B vector idx is 8 pixels of line
-// rc = idx / (rsw_ld / 8), i.e. of channel rc % C of staged row rc / C. A
-// vector whose 8 pixels lie inside the image on a w-contiguous x (NCHW, the
-// data blob) is ONE 16 B load, 2-byte aligned; anything else -- image
-// edges, other layouts -- takes guarded 2-byte loads. Thread tid of NT holds
-// vectors tid, tid + NT, ... (NV of them). Offsets inside one image are
-// 32-bit (the caller checks the extent).
-typedef __bf16 rf_uvec8 __attribute__((ext_vector_type(8), aligned(2)));
+// channel-planar (ps_rowfused.h): its 16 B vector idx is 8 pixels of one
+// channel of one staged row. ps_rf_vec decides per vector: nothing to load
+// (ZERO), ONE 2-byte-aligned 16 B load that may run over a row end into the
+// neighbouring row of the same tensor (WIDE), or 8 two-byte loads from
+// pixels clamped into the row (NARROW: the ends of x's span, layouts with
+// sw != 1). rf_load_x only issues loads -- no loaded value is used, so no
+// wait stands between them; rf_store_x packs the NARROW elements, zeroes
+// what lies outside the row with a register mask and writes the vector.
+// Thread tid of NT holds vectors tid, tid + NT, ... (NV of them).
+typedef unsigned rf_u32x4a2 __attribute__((ext_vector_type(4), aligned(2)));
+typedef unsigned rf_u32x4 __attribute__((ext_vector_type(4)));
+
+// a vector in flight. WIDE: the 16 B in w; NARROW: element j, zero-extended,
+// in e[j]. The two kinds keep registers of their own, so that neither load
+// has to be merged with the other's result before the store.
+// m = kind | lo << 2 | hi << 6
+struct RfRaw {
+  unsigned w[4];
+  unsigned e[8];
+  int m;
+};
+
+// the tile-invariant half of the decision (ps_rf_vec_pos), packed:
+// sc = sr << 16 | col, negative past the window
+struct RfPos {
+  int rel, sc;
+};
 
 template <int NV, int NT>
-__device__ inline void rf_load_x(bf16x8 (&xv)[NV], const RowFusedTiling& t,
-                                 const RowFusedTile& tl, const RfX& X,
-                                 int tid, int first) {
-  const int vpr = t.rsw_ld / 8;
-  const int total = t.srows * t.C * vpr;
-  const int iw0 = tl.ow0 * t.sw - t.pw;
-  const int ih0 = tl.oh0 * t.sh - t.ph;
-  const __bf16* xn = X.x + tl.n * X.sn;
+__device__ inline void rf_positions(RfPos (&pos)[NV], const RowFusedTiling& t,
+                                    const RfX& X, int tid, int first) {
 #pragma unroll
   for (int v = 0; v < NV; ++v) {
-    const int idx = first + tid + v * NT;
-    const int rc = idx / vpr;
-    const int sr = rc / t.C;
-    const int c = rc - sr * t.C;
-    const int ih = ih0 + sr;
-    const int iw = iw0 + (idx - rc * vpr) * 8;
+    const RowFusedVecPos p = ps_rf_vec_pos(t, X.g, first + tid + v * NT);
+    pos[v].rel = p.rel;
+    pos[v].sc = p.live ? p.sr << 16 | p.col : -1;
+  }
+}
+
+template <int NV>
+__device__ inline void rf_load_x(RfRaw (&xr)[NV], const RfPos (&pos)[NV],
+                                 const RowFusedTiling& t,
+                                 const RowFusedTile& tl, const RfX& X) {
 #pragma unroll
-    for (int j = 0; j < 8; ++j) xv[v][j] = (__bf16)0.0f;
-    if (idx < total && ih >= 0 && ih < t.H) {
-      const __bf16* src = xn + (ih * X.sh + c * X.sc);
-      if (X.sw == 1 && iw >= 0 && iw + 8 <= t.W) {
-        xv[v] = *reinterpret_cast<const rf_uvec8*>(src + iw);
-      } else {
+  for (int v = 0; v < NV; ++v) {
+    const RowFusedVecPos p = {pos[v].sc >> 16, pos[v].sc & 0xffff, pos[v].rel,
+                              pos[v].sc >= 0};
+    const RowFusedVec d = ps_rf_vec_at(t, tl, X.g, p);
+    xr[v].m = d.kind | d.lo << 2 | d.hi << 6;
 #pragma unroll
-        for (int j = 0; j < 8; ++j)
-          if (iw + j >= 0 && iw + j < t.W) xv[v][j] = src[(iw + j) * X.sw];
-      }
+    for (int j = 0; j < 4; ++j) xr[v].w[j] = 0u;
+    // e is read only where the kind is NARROW; starting it from a value the
+    // compiler cannot fold keeps the packing shifts out of the branch below
+    // (and with them a wait per vector). This steers code generation and a
+    // compiler update can undo it. What to look for in the ISA of
+    // conv_rowfused_fwd_k<6>: the six slots of a chunk are
+    // global_load_dwordx4, 8 x global_load_ushort, six times, with no
+    // s_waitcnt vmcnt between them. If waits come back they sit inside the
+    // NARROW branch: layouts with sw != 1 then stage one vector at a time;
+    // the w-contiguous data blob, which hardly has NARROW vectors, loses
+    // nothing
+#pragma unroll
+    for (int j = 0; j < 8; ++j) xr[v].e[j] = (unsigned)xr[v].m;
+    if (d.kind == PS_RF_WIDE) {
+      const rf_u32x4a2 w = *reinterpret_cast<const rf_u32x4a2*>(X.x + d.off);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) xr[v].w[j] = w[j];
+    }
+    if (d.kind == PS_RF_NARROW) {
+#pragma unroll
+      for (int j = 0; j < 8; ++j)
+        xr[v].e[j] = *reinterpret_cast<const unsigned short*>(
+            X.x + ps_rf_narrow_off(t, d, X.g.sw, j));
     }
   }
 }
 
 template <int NV, int NT>
-__device__ inline void rf_store_x(char* img, const bf16x8 (&xv)[NV],
+__device__ inline void rf_store_x(char* img, const RfRaw (&xr)[NV],
                                   const RowFusedTiling& t, int tid,
                                   int first) {
   const int total = t.srows * t.C * (t.rsw_ld / 8);
 #pragma unroll
   for (int v = 0; v < NV; ++v) {
     const int idx = first + tid + v * NT;
+    const int m = xr[v].m;
+    const bool narrow = (m & 3) == PS_RF_NARROW;
+    const unsigned em = ps_rf_elem_mask((m >> 2) & 15, m >> 6);
+    rf_u32x4 o;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const unsigned w = narrow ? xr[v].e[2 * i] | xr[v].e[2 * i + 1] << 16
+                                : xr[v].w[i];
+      const unsigned keep = ((em >> (2 * i) & 1u) ? 0x0000ffffu : 0u) |
+                            ((em >> (2 * i + 1) & 1u) ? 0xffff0000u : 0u);
+      o[i] = w & keep;
+    }
     if (idx < total)
-      *reinterpret_cast<bf16x8*>(img + PS_RF_HDR + idx * 16) = xv[v];
+      *reinterpret_cast<rf_u32x4*>(img + PS_RF_HDR + idx * 16) = o;
   }
 }
 
@@ -122,9 +169,11 @@ __device__ inline void rf_stage_x(char* img, const RowFusedTiling& t,
                                   int ptid) {
   const int total = t.srows * t.C * (t.rsw_ld / 8);
   for (int first = 0; first < total; first += RF_FV * RF_STAGERS) {
-    bf16x8 xv[RF_FV];
-    rf_load_x<RF_FV, RF_STAGERS>(xv, t, tl, X, ptid, first);
-    rf_store_x<RF_FV, RF_STAGERS>(img, xv, t, ptid, first);
+    RfPos pos[RF_FV];
+    RfRaw xr[RF_FV];
+    rf_positions<RF_FV, RF_STAGERS>(pos, t, X, ptid, first);
+    rf_load_x<RF_FV>(xr, pos, t, tl, X);
+    rf_store_x<RF_FV, RF_STAGERS>(img, xr, t, ptid, first);
   }
 }
 
@@ -177,6 +226,21 @@ void conv_rowfused_fwd_k(RowFusedTiling t, RfX X,
     pf[f] = (wid & 3) * 32 + f * 16 + l;
     pbf[f] = ps_rf_pbase(t, pf[f]);
   }
+  // the lane's bias values, once per launch and waited for here: a load
+  // still pending when the tile loop is entered (or one inside the epilogue)
+  // makes the compiler put a vmcnt(0) -- a drain of every store before it --
+  // in front of each of the epilogue's conditional stores. The empty asm
+  // below only forces that wait, and a compiler update can undo it. What to
+  // look for in the ISA of conv_rowfused_fwd_k<6>: the epilogue's
+  // global_store_short come 12 in a row with no s_waitcnt vmcnt between
+  // them. If the waits come back, AlexNet's conv1 forward goes from about
+  // 193 us back to about 324 us (profiles/first_layer_rowfused.md)
+  float bvf[FN];
+#pragma unroll
+  for (int fn = 0; fn < FN; ++fn)
+    bvf[fn] = bias && fn * 16 + l < t.Co ? bias[fn * 16 + l] : 0.0f;
+#pragma unroll
+  for (int fn = 0; fn < FN; ++fn) asm volatile("" : "+v"(bvf[fn]));
   __syncthreads();
 
   for (int64_t ti = t0; ti < t1; ++ti) {
@@ -194,10 +258,12 @@ void conv_rowfused_fwd_k(RowFusedTiling t, RfX X,
         for (int f = 0; f < 2; ++f)
           pb[f] = pf[f] < tl.nlive ? pbf[f] : PS_RF_NEG;
         f32x4 acc[2][FN] = {};
-        // two k-steps per trip (Kpad % 64 == 0): the second step's table and
-        // staged reads go out under the first step's MFMAs -- with one
-        // computing wave per SIMD nothing else hides the LDS latency
-#pragma unroll 2
+        // one k-step per trip: table reads, 16 two-byte staged reads, then
+        // the 12 MFMAs. Nothing of step s + 1 is issued under step s's MFMAs
+        // (an unroll pragma here changed nothing: the compiler keeps the
+        // steps apart), and with one computing wave per SIMD nothing else
+        // hides the LDS latency -- the next thing to work on
+        // (profiles/first_layer_rowfused.md)
         for (int ks = 0; ks < t.Kpad; ks += 32) {
           const rf_i32x4 k0 =
               *reinterpret_cast<const rf_i32x4*>(&kofft[ks + q * 8]);
@@ -232,7 +298,7 @@ void conv_rowfused_fwd_k(RowFusedTiling t, RfX X,
           for (int fn = 0; fn < FN; ++fn) {
             const int col = fn * 16 + l;
             if (col >= t.Co) continue;
-            const float bv = bias ? bias[col] : 0.0f;
+            const float bv = bvf[fn];
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
               const int p = wid * 32 + f * 16 + q * 4 + r;
@@ -299,15 +365,25 @@ void conv_rowfused_wgrad_k(RowFusedTiling t, RfX X,
   // registers ahead of the previous tile's MFMAs, stored to LDS after them
   const int my_pb = tid < PS_RF_TM ? ps_rf_pbase(t, tid) : 0;
   const int cv8 = t.Cop / 8;
-  bf16x8 xv[PS_RF_XV], dv[PS_RF_DV];
+  RfPos xpos[PS_RF_XV];
+  rf_positions<PS_RF_XV, RF_THREADS>(xpos, t, X, tid, 0);
+  // dy vector v of this thread: position and first column, tile-invariant
+  int dyp[PS_RF_DV], dyc[PS_RF_DV];
+#pragma unroll
+  for (int v = 0; v < PS_RF_DV; ++v) {
+    const int idx = tid + v * RF_THREADS;
+    dyp[v] = idx / cv8;
+    dyc[v] = (idx - dyp[v] * cv8) * 8;
+  }
+  RfRaw xr[PS_RF_XV];
+  bf16x8 dv[PS_RF_DV];
   auto load = [&](int64_t ti) {
     const RowFusedTile tl = ps_rf_tile(t, ti);
-    rf_load_x<PS_RF_XV, RF_THREADS>(xv, t, tl, X, tid, 0);
+    rf_load_x<PS_RF_XV>(xr, xpos, t, tl, X);
 #pragma unroll
     for (int v = 0; v < PS_RF_DV; ++v) {
-      const int idx = tid + v * RF_THREADS;
-      const int p = idx / cv8;
-      const int cv = (idx - p * cv8) * 8;
+      const int p = dyp[v];
+      const int cv = dyc[v];
 #pragma unroll
       for (int j = 0; j < 8; ++j) dv[v][j] = (__bf16)0.0f;
       if (p < tl.nlive && cv < t.Co)
@@ -317,14 +393,13 @@ void conv_rowfused_wgrad_k(RowFusedTiling t, RfX X,
   };
   auto store = [&](int buf, int64_t ti) {
     const RowFusedTile tl = ps_rf_tile(t, ti);
-    rf_store_x<PS_RF_XV, RF_THREADS>(xs0 + buf * t.xs_bytes, xv, t, tid,
+    rf_store_x<PS_RF_XV, RF_THREADS>(xs0 + buf * t.xs_bytes, xr, t, tid,
                                      0);
     __bf16* dyl = dyl0 + buf * dy_tile;
 #pragma unroll
     for (int v = 0; v < PS_RF_DV; ++v) {
-      const int idx = tid + v * RF_THREADS;
-      const int p = idx / cv8;
-      const int cv = (idx - p * cv8) * 8;
+      const int p = dyp[v];
+      const int cv = dyc[v];
       if (p < PS_RF_TM)
         *reinterpret_cast<bf16x8*>(&dyl[p * t.dy_ld + cv]) = dv[v];
     }
@@ -495,10 +570,11 @@ int ps_rowfused_prepare() {
 // y[NP][Co] = relu?(col @ wk^T + bias), col never materialized. x bf16 read
 // through its element strides; wk the bf16 khwc shadow [Co][t->Kpad].
 void ps_conv_rowfused_fwd(const RowFusedTiling* t, const void* x, int64_t sn,
-                          int64_t sc, int64_t sh, int64_t sw, const void* wk,
-                          const float* bias, void* y, int relu,
-                          hipStream_t s) {
-  const ps::RfX X = {(const __bf16*)x, sn, (int)sc, (int)sh, (int)sw};
+                          int64_t sc, int64_t sh, int64_t sw, int64_t span,
+                          const void* wk, const float* bias, void* y,
+                          int relu, hipStream_t s) {
+  const ps::RfX X = {(const __bf16*)x,
+                     {sn, (int)sc, (int)sh, (int)sw, span}};
   const int fn = t->Cop / 16;
   if (fn <= 1) ps::rf_launch_fwd<1>(*t, X, wk, bias, y, relu, s);
   else if (fn <= 2) ps::rf_launch_fwd<2>(*t, X, wk, bias, y, relu, s);
@@ -511,9 +587,10 @@ void ps_conv_rowfused_fwd(const RowFusedTiling* t, const void* x, int64_t sn,
 // entry (prezeroed), else it is cleared here first.
 void ps_conv_rowfused_wgrad(const RowFusedTiling* t, const void* x,
                             int64_t sn, int64_t sc, int64_t sh, int64_t sw,
-                            const void* dy, float* dwk, int prezeroed,
-                            hipStream_t s) {
-  const ps::RfX X = {(const __bf16*)x, sn, (int)sc, (int)sh, (int)sw};
+                            int64_t span, const void* dy, float* dwk,
+                            int prezeroed, hipStream_t s) {
+  const ps::RfX X = {(const __bf16*)x,
+                     {sn, (int)sc, (int)sh, (int)sw, span}};
   if (!prezeroed)
     PS_HIP_CHECK(hipMemsetAsync(
         dwk, 0, (size_t)t->Co * t->Kpad * sizeof(float), s));

@@ -222,14 +222,16 @@ void ps_data_transform_bf16(const uint8_t*, const int*, const float*, void*,
                             const TransformGeom*, hipStream_t);
 
 // conv_rowfused.hip: row-fused first layer (ps_rowfused.h), bf16 only. x is
-// read through its element strides (sn, sc, sh, sw); wk is the khwc shadow
-// [Co][Kpad]; y / dy are NHWC rows; dwk is f32 [Co][Kpad], added to
-// atomically (cleared first unless prezeroed).
+// read through its element strides (sn, sc, sh, sw) and never outside its
+// element span [0, span) (RowFusedX); wk is the khwc shadow [Co][Kpad];
+// y / dy are NHWC rows; dwk is f32 [Co][Kpad], added to atomically (cleared
+// first unless prezeroed).
 void ps_conv_rowfused_fwd(const RowFusedTiling*, const void* x, int64_t sn,
-                          int64_t sc, int64_t sh, int64_t sw, const void* wk,
-                          const float* bias, void* y, int relu, hipStream_t);
+                          int64_t sc, int64_t sh, int64_t sw, int64_t span,
+                          const void* wk, const float* bias, void* y,
+                          int relu, hipStream_t);
 void ps_conv_rowfused_wgrad(const RowFusedTiling*, const void* x, int64_t sn,
-                            int64_t sc, int64_t sh, int64_t sw,
+                            int64_t sc, int64_t sh, int64_t sw, int64_t span,
                             const void* dy, float* dwk, int prezeroed,
                             hipStream_t);
 // once per process, when a plan comes out row-fused: reads the CU count and

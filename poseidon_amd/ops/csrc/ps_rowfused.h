@@ -1,7 +1,8 @@
 // Row-fused first-layer convolution: tile walk, staged-row addressing and LDS
 // sizing, shared by the planner (ps_conv_plan.h), the kernels
-// (conv_rowfused.hip) and a stand-alone host program
-// (tests/rowfused_plan_host.cpp). Plain C++, no torch / HIP includes.
+// (conv_rowfused.hip) and two stand-alone host programs
+// (tests/rowfused_plan_host.cpp, tests/rowfused_stage_host.cpp). Plain C++,
+// no torch / HIP includes.
 //
 // A TILE is PS_RF_TM consecutive output positions of one image:
 //   full-row mode (Wo <= TM): R = min(TM / Wo, Ho) whole output rows,
@@ -15,8 +16,10 @@
 // lines of rsw_ld bf16: line sr*C + c holds channel c of input row
 // ih = oh0*sh - ph + sr, its element w is pixel iw = ow0*sw - pw + w; pixels
 // outside the image are zeros. Planar, because the data blob is NCHW: a line
-// is then one contiguous run of x and stages with 16 B loads (an interleaved
-// image needs a 2-byte load per element, which measured 8 us per tile). The
+// is then one contiguous run of x and stages with 16 B loads (ps_rf_vec
+// below). An interleaved image, whose operand reads would be contiguous, has
+// not been measured with such loads; the one form tried staged it with a
+// 2-byte load per element. The
 // im2col entry (position p, k = (ky, kx, c)) is the staged element
 // pbase(p) + koff(k)  with
 //   pbase(p) = (p / WS)*sh*C*rsw_ld + (p % WS)*sw
@@ -160,4 +163,110 @@ PS_RF_HD inline int ps_rf_koff(const RowFusedTiling& t, int k) {
 PS_RF_HD inline int ps_rf_addr(int pbase, int koff) {
   const int a = pbase + koff;
   return a < 0 ? 0 : a;
+}
+
+// ---- staging one 16 B vector of a window ----------------------------------
+// x as the kernels see it: element strides, and the element span of the
+// tensor from its first element, 1 + sum (size_i - 1) * stride_i. Elements
+// [0, span) are mapped memory of x's storage whatever the layout; nothing
+// else may be touched.
+struct RowFusedX {
+  int64_t sn;      // image stride
+  int sc, sh, sw;  // strides inside one image (one image spans < 2^31)
+  int64_t span;
+};
+
+// Vector idx of a tile's staged image is pixels iw .. iw + 7 of channel c of
+// input row ih (idx -> line rc = idx / (rsw_ld / 8), rc -> (sr, c)). How it
+// is fetched:
+//   ZERO:   the row is outside the image, idx is past the window, or none of
+//           the 8 pixels is inside the row. No load.
+//   WIDE:   sw == 1 and the 8 elements at off lie inside [0, span), whether
+//           or not they lie inside the row: ONE 16 B load (2-byte aligned).
+//           Pixels past a row end are the next row's first, pixels before a
+//           row start the previous row's last: memory of the same tensor.
+//   NARROW: the rest -- the few vectors at the two ends of the span, and any
+//           layout with sw != 1. 8 two-byte loads, element j from pixel
+//           clamp(iw + j, 0, W - 1) of the row (ps_rf_narrow_off).
+// Either way elements outside [lo, hi) are zeroed in registers afterwards
+// (ps_rf_elem_mask), so the staged bytes are the window of the header
+// comment: pixels outside the image are zeros.
+enum { PS_RF_ZERO = 0, PS_RF_WIDE = 1, PS_RF_NARROW = 2 };
+
+struct RowFusedVec {
+  int kind;
+  int lo, hi;   // live elements of the 8: lo <= j < hi
+  int iw;       // pixel of element 0 (may be negative)
+  int64_t off;  // WIDE: element 0; NARROW: pixel 0 of the row
+};
+
+// the part of the decision that does not depend on the tile: which staged
+// row and column vector idx is, and its row's offset from the window's
+// first row. A kernel keeps these across its tiles (two divisions saved per
+// vector and tile).
+struct RowFusedVecPos {
+  int sr;     // staged row
+  int col;    // column of element 0 inside the staged line
+  int rel;    // sr * sh + c * sc, in elements of x
+  bool live;  // idx is inside the window
+};
+
+PS_RF_HD inline RowFusedVecPos ps_rf_vec_pos(const RowFusedTiling& t,
+                                             const RowFusedX& X, int idx) {
+  RowFusedVecPos p;
+  const int vpr = t.rsw_ld / 8;
+  const int rc = idx / vpr;
+  p.sr = rc / t.C;
+  p.col = (idx - rc * vpr) * 8;
+  p.rel = p.sr * X.sh + (rc - p.sr * t.C) * X.sc;
+  p.live = idx < t.srows * t.C * vpr;
+  return p;
+}
+
+PS_RF_HD inline RowFusedVec ps_rf_vec_at(const RowFusedTiling& t,
+                                         const RowFusedTile& tl,
+                                         const RowFusedX& X,
+                                         const RowFusedVecPos& p) {
+  RowFusedVec d;
+  const int ih0 = tl.oh0 * t.sh - t.ph;
+  const int ih = ih0 + p.sr;
+  d.iw = tl.ow0 * t.sw - t.pw + p.col;
+  d.lo = d.iw < 0 ? (d.iw < -8 ? 8 : -d.iw) : 0;
+  d.hi = t.W - d.iw < 8 ? (t.W - d.iw < 0 ? 0 : t.W - d.iw) : 8;
+  d.kind = PS_RF_ZERO;
+  d.off = 0;
+  if (!p.live || ih < 0 || ih >= t.H || d.lo >= d.hi) {
+    d.lo = d.hi = 0;
+    return d;
+  }
+  const int64_t row = tl.n * X.sn + (ih0 * X.sh + p.rel);
+  const int64_t first = row + d.iw;
+  if (X.sw == 1 && first >= 0 && first + 8 <= X.span) {
+    d.kind = PS_RF_WIDE;
+    d.off = first;
+  } else {
+    d.kind = PS_RF_NARROW;
+    d.off = row;
+  }
+  return d;
+}
+
+PS_RF_HD inline RowFusedVec ps_rf_vec(const RowFusedTiling& t,
+                                      const RowFusedTile& tl,
+                                      const RowFusedX& X, int idx) {
+  return ps_rf_vec_at(t, tl, X, ps_rf_vec_pos(t, X, idx));
+}
+
+// NARROW: the element that stands in for element j (a live j is its own
+// pixel; a dead one repeats the row's nearest pixel and is masked away)
+PS_RF_HD inline int64_t ps_rf_narrow_off(const RowFusedTiling& t,
+                                         const RowFusedVec& d, int sw, int j) {
+  int px = d.iw + j;
+  px = px < 0 ? 0 : px > t.W - 1 ? t.W - 1 : px;
+  return d.off + (int64_t)px * sw;
+}
+
+// bit j set: element j of the vector is kept
+PS_RF_HD inline unsigned ps_rf_elem_mask(int lo, int hi) {
+  return ((1u << hi) - 1u) & ~((1u << lo) - 1u);
 }
