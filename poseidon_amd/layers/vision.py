@@ -300,9 +300,6 @@ class LRNLayer(Layer):
         self._tail_pool = None  # consumer pool whose backward we gather
         self._tail_pool_top = None  # ... and its top blob (we read the diff)
         self._dx_cache = None
-        if self.region == "WITHIN_CHANNEL":
-            # composite: x^2 -> ave-pool(size) -> scale -> x * scale^-beta
-            self.pre_pad = (self.size - 1) // 2
 
     def reshape(self, bottom, top) -> None:
         top[0].reshape(bottom[0].shape)
@@ -311,14 +308,14 @@ class LRNLayer(Layer):
         x = bottom[0].data
         if self.region == "ACROSS_CHANNELS":
             y, scale = ops.lrn_forward(x, self.size, self.alpha, self.beta)
+            self._y = y
         else:
-            k = (self.size, self.size)
-            sq = x * x
-            avg = ops.pool_ave_forward(sq, k, (1, 1), (self.pre_pad, self.pre_pad))
-            scale = 1.0 + self.alpha * avg
-            y = x * scale.pow(-self.beta)
+            # the fused kernels return no scale: their backward recomputes
+            # it and reads no y, so neither is kept
+            y, scale = ops.lrn_within_forward(x, self.size, self.alpha,
+                                              self.beta)
+            self._y = None if scale is None else y
         self._scale = scale
-        self._y = y
         top[0].data = y
 
     def backward(self, top, propagate_down, bottom) -> None:
@@ -343,14 +340,13 @@ class LRNLayer(Layer):
             bottom[0].diff = ops.lrn_backward(x, self._y, self._scale, dy,
                                               self.size, self.alpha, self.beta)
         else:
-            scale = self._scale
-            k = (self.size, self.size)
-            # dx = dy*scale^-b - 2*a*b/size^2-less: within-channel window avg
-            ratio = dy * self._y / scale
-            spread = ops.pool_ave_backward(ratio, bottom[0].shape, k, (1, 1),
-                                           (self.pre_pad, self.pre_pad))
-            bottom[0].diff = dy * scale.pow(-self.beta) \
-                - 2.0 * self.alpha * self.beta * x * spread
+            dx = ops.lrn_within_backward(x, dy, self.size, self.alpha,
+                                         self.beta, y=self._y,
+                                         scale=self._scale,
+                                         dx_out=self._dx_cache)
+            if self._scale is None:  # fused: keep the buffer it wrote
+                self._dx_cache = dx
+            bottom[0].diff = dx
 
 
 @register_layer("IM2COL")

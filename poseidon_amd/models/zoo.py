@@ -109,12 +109,15 @@ class NetBuilder:
             pp.pad = pad
         return lp
 
-    def lrn(self, name, bottom, top, local_size=5, alpha=1e-4, beta=0.75):
+    def lrn(self, name, bottom, top, local_size=5, alpha=1e-4, beta=0.75,
+            norm_region=None):
         lp = self._layer("LRN", name, bottom, top)
         p = lp.ensure("lrn_param")
         p.local_size = local_size
         p.alpha = alpha
         p.beta = beta
+        if norm_region is not None:
+            p.norm_region = norm_region
         return lp
 
     def dropout(self, name, blob, ratio=0.5):
@@ -175,6 +178,30 @@ def cifar10_quick(batch: int = 100, num_classes: int = 10) -> Message:
     b.ip("ip1", "pool3", "ip1", 64, w_std=0.1)
     b.ip("ip2", "ip1", "ip2", num_classes, w_std=0.1)
     b.softmax_loss("loss", "ip2", "label")
+    return b.build()
+
+
+def cifar10_full(batch: int = 100, num_classes: int = 10) -> Message:
+    """CIFAR-10 full (examples/cifar10/cifar10_full_train_test.prototxt):
+    three conv blocks, WITHIN_CHANNEL LRN after the first two, one
+    classifier whose weights decay 250 times as fast."""
+    b = NetBuilder("CIFAR10_full")
+    b.synthetic_images(batch, 3, 32, num_classes)
+    norm = dict(local_size=3, alpha=5e-5, beta=0.75,
+                norm_region="WITHIN_CHANNEL")
+    b.conv("conv1", "data", "conv1", 32, 5, pad=2, w_std=0.0001)
+    b.pool("pool1", "conv1", "pool1", "MAX", 3, 2)
+    b.relu("relu1", "pool1")
+    b.lrn("norm1", "pool1", "norm1", **norm)
+    b.conv("conv2", "norm1", "conv2", 32, 5, pad=2, w_std=0.01)
+    b.relu("relu2", "conv2")
+    b.pool("pool2", "conv2", "pool2", "AVE", 3, 2)
+    b.lrn("norm2", "pool2", "norm2", **norm)
+    b.conv("conv3", "norm2", "conv3", 64, 5, pad=2, w_std=0.01)
+    b.relu("relu3", "conv3")
+    b.pool("pool3", "conv3", "pool3", "AVE", 3, 2)
+    b.ip("ip1", "pool3", "ip1", num_classes, w_std=0.01, decay=(250.0, 0.0))
+    b.softmax_loss("loss", "ip1", "label")
     return b.build()
 
 
@@ -349,6 +376,7 @@ def vgg16(batch: int = 32, num_classes: int = 1000) -> Message:
 MODEL_ZOO = {
     "lenet": lenet,
     "cifar10_quick": cifar10_quick,
+    "cifar10_full": cifar10_full,
     "alexnet": alexnet,
     "caffenet": caffenet,
     "googlenet": googlenet,

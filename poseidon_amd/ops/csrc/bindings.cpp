@@ -1023,6 +1023,49 @@ Tensor lrn_backward(const Tensor& x, const Tensor& y, const Tensor& scale,
   return dx;
 }
 
+// WITHIN_CHANNEL LRN (lrn_within.hip): one kernel each way, no scale tensor.
+void lrn_within_check(const Tensor& x, int size) {
+  check_float_like(x, "x");
+  TORCH_CHECK(x.dim() == 4 &&
+              ps_lrn_within_ok((int)x.size(1), size, (int)x.element_size()),
+              "lrn_within: needs a 4D tensor and size 3, 5 or 7");
+}
+
+Tensor lrn_within_forward(const Tensor& x, int size, double alpha,
+                          double beta) {
+  lrn_within_check(x, size);
+  auto x_cl = cl4(x);
+  Tensor y = empty_cl(x.sizes(), x.options());
+  PS_CALL(lrn_within_fwd, is_bf16(x), P(x_cl), P(y), (int)x.size(0),
+          (int)x.size(1), (int)x.size(2), (int)x.size(3), size, (float)alpha,
+          (float)beta, stream());
+  return y;
+}
+
+Tensor lrn_within_backward(const Tensor& x, const Tensor& dy, int size,
+                           double alpha, double beta,
+                           const c10::optional<Tensor>& dx_out) {
+  lrn_within_check(x, size);
+  TORCH_CHECK(dy.sizes() == x.sizes() && dy.is_cuda() &&
+              dy.scalar_type() == x.scalar_type(),
+              "lrn_within: dy must match x");
+  auto x_cl = cl4(x);
+  auto dy_cl = cl4(dy);
+  Tensor dx = reuse_or_empty_cl(dx_out, x.sizes(), x);
+  TORCH_CHECK(dx.data_ptr() != x_cl.data_ptr() &&
+              dx.data_ptr() != dy_cl.data_ptr() && dx.is_cuda() &&
+              dx.is_contiguous(at::MemoryFormat::ChannelsLast),
+              "lrn_within: dx_out must be a distinct channels-last tensor");
+  PS_CALL(lrn_within_bwd, is_bf16(x), P(x_cl), P(dy_cl), P(dx),
+          (int)x.size(0), (int)x.size(1), (int)x.size(2), (int)x.size(3), size,
+          (float)alpha, (float)beta, stream());
+  return dx;
+}
+
+int64_t lrn_within_launches(bool reset) {
+  return ps_lrn_within_launches(reset ? 1 : 0);
+}
+
 // ---------------------------------------------------------------------------
 // Fused backward tails of a conv block (conv -> relu -> [lrn] -> [max pool]):
 // one pass over the conv output writes dx, already masked by the in-place
@@ -1833,6 +1876,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("relu_backward_bias", &relu_backward_bias);
   m.def("set_bwd_tail_blocks", &set_bwd_tail_blocks);
   m.def("lrn_v8_ok", &ps_lrn_v8_ok);
+  m.def("lrn_within_forward", &lrn_within_forward);
+  m.def("lrn_within_backward", &lrn_within_backward);
+  m.def("lrn_within_ok", &ps_lrn_within_ok);
+  m.def("lrn_within_launches", &lrn_within_launches);
+  m.def("set_lrn_within_strip", &ps_lrn_within_set_strip);
   m.def("softmax_forward", &softmax_forward);
   m.def("softmax_backward", &softmax_backward);
   m.def("softmax_loss_forward", &softmax_loss_forward);

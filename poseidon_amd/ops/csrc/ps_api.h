@@ -160,6 +160,23 @@ void ps_lrn_bwd_v8_tail_bf16(const void*, const void*, const void*,
                              int, int64_t, int, int, float, float, int,
                              hipStream_t);
 
+// lrn_within.hip: WITHIN_CHANNEL LRN on NHWC tensors, sizes 3 / 5 / 7.
+// fwd (x, y, N, C, H, W, size, alpha, beta); bwd (x, dy, dx, ...) recomputes
+// the scale. Not in place: x, dy and the output are distinct.
+int ps_lrn_within_ok(int C, int size, int itemsize);
+void ps_lrn_within_fwd_f32(const float*, float*, int, int, int, int, int,
+                           float, float, hipStream_t);
+void ps_lrn_within_fwd_bf16(const void*, void*, int, int, int, int, int,
+                            float, float, hipStream_t);
+void ps_lrn_within_bwd_f32(const float*, const float*, float*, int, int, int,
+                           int, int, float, float, hipStream_t);
+void ps_lrn_within_bwd_bf16(const void*, const void*, void*, int, int, int,
+                            int, int, float, float, hipStream_t);
+// tests only: rows a block emits (0 = the plan's own)
+void ps_lrn_within_set_strip(int n);
+// host-side count of the launches above
+int64_t ps_lrn_within_launches(int reset);
+
 // softmax.hip
 void ps_softmax_rows_f32(const float*, float*, int64_t, int, hipStream_t);
 void ps_softmax_bwd_rows_f32(const float*, const float*, float*, int64_t, int,

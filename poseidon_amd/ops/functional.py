@@ -487,6 +487,87 @@ def lrn_backward(x, y, scale, dy, size: int, alpha: float, beta: float):
 
 
 # ---------------------------------------------------------------------------
+# LRN (within channel): a size x size window of one channel, stride 1,
+# centred; the divisor is always size^2 (the average pool counts its padding
+# here) and alpha is not divided again.
+#   scale = 1 + alpha * avepool(x^2),  y = x * scale^-beta
+# GPU, sizes 3 / 5 / 7, fp32 or bf16: one kernel each way (lrn_within.hip),
+# fp32 inside, and the backward recomputes scale. Everything else runs the
+# composite around the average-pool ops, which is also the CPU path.
+# ---------------------------------------------------------------------------
+
+_lrn_within = os.environ.get("PS_LRN_WITHIN", "1") not in ("", "0")
+
+
+def set_lrn_within(on: bool) -> None:
+    """Toggle the fused WITHIN_CHANNEL LRN kernels (default on; the
+    environment variable PS_LRN_WITHIN=0/1 sets it at import). Off puts the
+    GPU back on the composite, for A/B runs. Nothing caches on it: eager
+    steps follow it at once, a captured graph keeps what it recorded."""
+    global _lrn_within
+    _lrn_within = bool(on)
+
+
+def lrn_within() -> bool:
+    return _lrn_within
+
+
+def _set_lrn_within_strip(n: int) -> None:
+    """Tests only: rows one block of the fused kernels emits (0 = the plan's
+    own), so that a small tensor crosses strip seams."""
+    if ext_available():
+        _ext().set_lrn_within_strip(int(n))
+
+
+def lrn_within_launches(reset: bool = False) -> int:
+    """Launches so far of the fused kernels (a host-side counter)."""
+    if not ext_available():
+        return 0
+    return int(_ext().lrn_within_launches(bool(reset)))
+
+
+def lrn_within_fused(x, size: int) -> bool:
+    """Whether lrn_within_forward / _backward run x on the fused kernels."""
+    return bool(_lrn_within and x.is_cuda and x.dim() == 4
+                and x.dtype in (torch.float32, torch.bfloat16)
+                and _ext().lrn_within_ok(x.shape[1], int(size),
+                                         x.element_size()))
+
+
+def _lrn_within_scale(x, size: int, alpha: float):
+    pad = (size - 1) // 2
+    avg = pool_ave_forward(x * x, (size, size), (1, 1), (pad, pad))
+    return 1.0 + alpha * avg
+
+
+def lrn_within_forward(x, size: int, alpha: float, beta: float):
+    """-> (y, scale). scale is None on the fused path, which keeps none."""
+    if lrn_within_fused(x, size):
+        return _ext().lrn_within_forward(x, size, alpha, beta), None
+    scale = _lrn_within_scale(x, size, alpha)
+    return x * scale.pow(-beta), scale
+
+
+def lrn_within_backward(x, dy, size: int, alpha: float, beta: float,
+                        y=None, scale=None, dx_out=None):
+    """y, scale: what the composite forward returned, recomputed when absent;
+    the fused path reads neither. dx_out: a buffer the fused path may reuse
+    (never x or dy: the kernel is not in place)."""
+    if lrn_within_fused(x, size):
+        return _ext().lrn_within_backward(x, dy, size, alpha, beta, dx_out)
+    if scale is None:
+        scale = _lrn_within_scale(x, size, alpha)
+    if y is None:
+        y = x * scale.pow(-beta)
+    pad = (size - 1) // 2
+    # dx = dy*scale^-b - 2*a*b/size^2-less: within-channel window avg
+    ratio = dy * y / scale
+    spread = pool_ave_backward(ratio, x.shape, (size, size), (1, 1),
+                               (pad, pad))
+    return dy * scale.pow(-beta) - 2.0 * alpha * beta * x * spread
+
+
+# ---------------------------------------------------------------------------
 # Fused backward tails of a conv block: conv -> relu -> [lrn] -> [max pool].
 # One kernel writes the conv's top diff (already masked by the in-place
 # ReLU) and adds its column sum into the conv's bias gradient. The CPU path

@@ -22,6 +22,7 @@ sources = [
         "elementwise.hip",
         "pool.hip",
         "lrn.hip",
+        "lrn_within.hip",
         "softmax.hip",
         "sgd.hip",
         "im2col.hip",
