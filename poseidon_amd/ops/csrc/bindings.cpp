@@ -177,6 +177,17 @@ const void* zero_page(const Tensor& like) {
   return z.data_ptr();
 }
 
+// Skinny split-K plans (ps_gemm_plan.h): fc forward and data-gradient GEMMs
+// at batch-sized M choose tile and split depth together so that the grid
+// fills the chip. Default ON: see docs/performance.md item 31.
+// PS_SKINNY_SPLITK=0/1 sets the switch at load; kmin / bm / bn / splitk are
+// for tests and tuning runs.
+void set_skinny_splitk(bool on, int kmin, int bm, int bn, int splitk) {
+  ps_gemm_set_skinny(on ? (kmin > 0 ? kmin : PS_SKINNY_KMIN) : 0, bm, bn,
+                     splitk);
+}
+bool skinny_splitk() { return ps_gemm_skinny_kmin() > 0; }
+
 // C[M,N] = alpha * op(A) @ op(B) (+ bias, relu) + beta * C at element
 // offsets into A/B/C. A/B share a dtype; C is fp32 or matches them.
 void run_gemm(const Tensor& A, const Tensor& B, Tensor& C,
@@ -232,8 +243,11 @@ Tensor gemm(const Tensor& A, const Tensor& B, int M, int N, int K,
 
 // The plan gemm() above would run for this shape right now (tests, tuning):
 // path, tile, split-K depth, K slice and workspace size.
+// out_f32 = false plans a C of the input type, bias = true one with a bias
+// (an address is all planning reads of it): what linear_forward and
+// linear_backward's dx run, which cannot take atomics.
 py::dict gemm_plan(int M, int N, int K, bool a_klast, bool b_klast,
-                   bool bf16) {
+                   bool bf16, bool out_f32, bool bias) {
   GemmArgs g{};
   // planning reads the operands' alignment only; gemm() passes fresh
   // allocations, which are 256 B aligned
@@ -246,10 +260,12 @@ py::dict gemm_plan(int M, int N, int K, bool a_klast, bool b_klast,
   g.alpha = 1.0f;
   g.a_klast = a_klast; g.b_klast = b_klast;
   g.in_bf16 = bf16;
-  g.out_f32 = true;
+  g.out_f32 = out_f32 || !bf16;
+  if (bias) g.bias = reinterpret_cast<const float*>(uintptr_t{256});
   GemmPlan p;
   ps_gemm_plan(&g, &p);
   py::dict d;
+  d["skinny"] = p.skinny;
   d["tr16"] = p.tr16;
   d["splitk"] = p.splitk;
   d["ws_elems"] = p.ws_elems;
@@ -1830,7 +1846,14 @@ void data_transform(const Tensor& raw, const Tensor& params,
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("data_transform", &data_transform);
   m.def("gemm", &gemm);
-  m.def("gemm_plan", &gemm_plan);
+  m.def("gemm_plan", &gemm_plan, py::arg("M"), py::arg("N"), py::arg("K"),
+        py::arg("a_klast"), py::arg("b_klast"), py::arg("bf16"),
+        py::arg("out_f32") = true, py::arg("bias") = false);
+  // PS_SKINNY_SPLITK=0/1 is read where the switch lives (gemm.hip)
+  m.def("set_skinny_splitk", &set_skinny_splitk, py::arg("on"),
+        py::arg("kmin") = 0, py::arg("bm") = 0, py::arg("bn") = 0,
+        py::arg("splitk") = 0);
+  m.def("skinny_splitk", &skinny_splitk);
   m.def("linear_forward", &linear_forward);
   m.def("linear_backward", &linear_backward);
   m.def("gemm_at_b", &gemm_at_b);

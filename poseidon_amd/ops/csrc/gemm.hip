@@ -1057,6 +1057,14 @@ static bool tn_tr_operands_ok(const GemmArgs& g) {
   return true;
 }
 
+// The skinny plan's switch and K-slice floor (0: off), PS_SKINNY_SPLITK=0/1
+// at load; the tune is for tests / tuning only and all zero in training.
+static std::atomic<int> g_skinny_kmin{[] {
+  const char* e = getenv("PS_SKINNY_SPLITK");
+  return e && *e && atoi(e) == 0 ? 0 : PS_SKINNY_KMIN;
+}()};
+static SkinnyTune g_skinny_tune = {0, 0, 0};
+
 static GemmShape gemm_shape(const GemmArgs& g) {
   GemmShape sh;
   sh.M = g.M;
@@ -1070,6 +1078,13 @@ static GemmShape gemm_shape(const GemmArgs& g) {
   sh.nt = g.a_klast && g.b_klast;
   sh.only128 = !g.a_klast && g.b_klast;
   sh.deterministic = ps_deterministic() != 0;
+  // the fc forward / data-gradient class: a K-last A. Gathered or not: a
+  // conv forward plans the same whether its column matrix exists or not
+  // (the two paths give the same bits, tests/test_gpu_gather_gemm.py)
+  if (g.a_klast && !g.gather_b) {
+    sh.skinny_kmin = g_skinny_kmin.load();
+    sh.skinny_tune = g_skinny_tune;
+  }
   return sh;
 }
 
@@ -1326,6 +1341,12 @@ int64_t ps_float_atomic_launches(int reset) {
 void ps_gemm_set_tr_tune(int bm, int bn, int target) {
   g_tr_tune = {bm, bn, target};
 }
+
+void ps_gemm_set_skinny(int kmin, int bm, int bn, int splitk) {
+  g_skinny_kmin.store(kmin > 0 ? kmin : 0);
+  g_skinny_tune = {bm, bn, splitk};
+}
+int ps_gemm_skinny_kmin() { return g_skinny_kmin.load(); }
 
 // ws: plan->ws_elems floats (null when the plan asks for none)
 void ps_gemm_run(const GemmArgs* g, const GemmPlan* plan, float* ws,

@@ -41,6 +41,11 @@ void ps_gemm_run(const GemmArgs* g, const GemmPlan* plan, float* ws,
                  hipStream_t s);
 // tests / tuning: force the tr16 tile and split-K block target (0 = planner)
 void ps_gemm_set_tr_tune(int bm, int bn, int target);
+// The skinny plan (ps_gemm_plan.h): kmin > 0 switches it on with that K-slice
+// floor, 0 switches it off; bm, bn, splitk force its tile and depth for
+// tests and tuning runs (0 = planner).
+void ps_gemm_set_skinny(int kmin, int bm, int bn, int splitk);
+int ps_gemm_skinny_kmin();
 
 // Deterministic mode, process-wide (initially PS_DETERMINISTIC=1): every
 // float reduction runs in an order fixed by the shape and the plan. No

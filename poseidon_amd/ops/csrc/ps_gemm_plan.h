@@ -25,6 +25,13 @@ struct GemmPlan {
   int kchunk;        // K per grid.z slice, a multiple of the staged K tile
   int M0, N0;        // tr16 only: interior extent (edge strips run generic)
   int ry, cx;        // generic only: 2D-XCD rectangle in tiles (0: none)
+  bool skinny;       // generic only: made by ps_skinny_plan (for reporting)
+};
+
+// Manual override of the skinny plan's tile and depth, 0 = planner's choice.
+// For tests and tuning runs; never set in the training path.
+struct SkinnyTune {
+  int bm, bn, splitk;
 };
 
 // What planning needs to know of a GEMM (no pointers: the caller folds
@@ -41,6 +48,11 @@ struct GemmShape {
   // deterministic mode: no plan may add into C atomically. A split takes
   // the f32 workspace + ordered reduce (ws_elems > 0), or does not happen.
   bool deterministic = false;
+  // > 0: a K-last A (the fc forward / data-gradient class, and a conv's
+  // rows when there are as few) and the skinny plan switched on; the value
+  // is the K-slice floor (PS_SKINNY_KMIN unless a tuning run sets it)
+  int skinny_kmin = 0;
+  SkinnyTune skinny_tune = {0, 0, 0};
 };
 
 // Manual override of the tr16 tile and split-K block target, 0 = planner's
@@ -352,6 +364,81 @@ inline void ps_pick_xcd_rect(const GemmShape& g, GemmPlan* p) {
   }
 }
 
+// ---------------------------------------------------------------------------
+// Skinny plan: thin tile grids whose C cannot take atomics (bf16 out, bias,
+// ReLU, beta) at batch-sized M -- the fc forward and data-gradient GEMMs. The
+// workspace branch of ps_generic_plan leaves most CUs without a block there
+// (AlexNet fc7, 256x4096x4096: 64 tiles x 2 slices on 512 slots; fc8's dx,
+// K = 1000, cannot split at all). These blocks are latency-bound, ~14 ns a
+// k-row at one 128x128 block per CU, and a second resident block overlaps
+// almost for free, so the plan fills the 512 slots:
+//   - depth = the deepest split that stays within the slots, floor(512 /
+//     tiles), whose slices as staged keep g.skinny_kmin k-rows and whose
+//     workspace fits PS_WS_CAP_BYTES. Going past the slots starts a second
+//     wave (fc6 dx, 144 tiles: 3 slices 59.6 us, 4 slices 80.8 us) and every
+//     slice is one more f32 tile written and read back, which is the charge
+//     for depth: past the floor the reduce grows faster than the GEMM shrinks.
+//   - tile = the menu's, unless it cannot reach 3/4 of the slots even at its
+//     deepest split and 64x64 gives more blocks (N = 1000: 16 tiles of
+//     128x128, 64 of 64x64; K = 1000: two slices at most). A 64x64 block costs
+//     ~10 ns a k-row for a quarter of the output, so it only pays there.
+//   - sk = ceil(K / kchunk): no slice is ever empty.
+// The split keeps the workspace and the separate splitk_reduce_k launch, in
+// slice order. Reducing inside the GEMM kernel (last block to arrive at a
+// per-tile counter) was built and measured slower at every depth on every
+// one of these shapes: the device-scope release each block needs before it
+// counts itself in costs more than the launch it saves
+// (profiles/fc_skinny_gemm.md).
+// ---------------------------------------------------------------------------
+constexpr int PS_SKINNY_MAX_M = 512;  // "skinny": M is a batch, not N*OH*OW
+constexpr int PS_SKINNY_KMIN = 512;   // default K-slice floor
+constexpr int PS_SKINNY_SLOTS = 2 * PS_NUM_CUS;
+
+// Depth of one candidate tile: (sk, kchunk) with sk * tiles <= slots, kchunk
+// a whole number of staged tiles >= kmin, no empty slice, workspace under
+// the cap. `force` > 0 asks for that depth instead of the slots' (tuning).
+inline int ps_skinny_depth(const GemmShape& g, int64_t tiles, int force) {
+  int64_t want = force > 0 ? force : PS_SKINNY_SLOTS / tiles;
+  const int64_t cap = PS_WS_CAP_BYTES / 4 / ((int64_t)g.M * g.N);
+  if (want > cap) want = cap;
+  if (want < 1) want = 1;
+  if (want > g.K) want = g.K;
+  // the slice as staged: K = 1000 makes two slices of 512
+  auto staged = [&](int64_t sk) {
+    return (int)(((g.K + sk - 1) / sk + g.bk - 1) / g.bk * g.bk);
+  };
+  if (force <= 0)
+    while (want > 1 && staged(want) < g.skinny_kmin) --want;
+  return (g.K + staged(want) - 1) / staged(want);
+}
+
+// Fills tile, depth and workspace of *p, whose bm x bn is the menu's tile on
+// entry (ps_generic_plan derives kchunk from the depth).
+inline void ps_skinny_plan(const GemmShape& g, GemmPlan* p) {
+  const SkinnyTune& t = g.skinny_tune;
+  p->skinny = true;
+  auto tiles_of = [&](int bm, int bn) {
+    return (int64_t)((g.M + bm - 1) / bm) * ((g.N + bn - 1) / bn);
+  };
+  if (t.bm > 0 && t.bn > 0 && ps_gemm_tile(t.bm, t.bn) &&
+      !ps_gemm_tile(t.bm, t.bn)->narrow_only) {
+    p->bm = t.bm;
+    p->bn = t.bn;
+  }
+  int sk = ps_skinny_depth(g, tiles_of(p->bm, p->bn), t.splitk);
+  if (t.bm <= 0 && tiles_of(p->bm, p->bn) * sk < PS_SKINNY_SLOTS * 3 / 4) {
+    const int sk64 = ps_skinny_depth(g, tiles_of(64, 64), t.splitk);
+    // not where 64 rows pad M further than the menu's tile does (M = 32)
+    if (tiles_of(64, 64) * sk64 > tiles_of(p->bm, p->bn) * sk &&
+        tiles_of(64, 64) * 64 * 64 <= tiles_of(p->bm, p->bn) * p->bm * p->bn) {
+      p->bm = p->bn = 64;
+      sk = sk64;
+    }
+  }
+  p->splitk = sk;
+  if (sk > 1) p->ws_elems = (int64_t)sk * g.M * g.N;
+}
+
 // Generic path, every launch decision: tile, split-K, K slice, rectangle.
 // Splits K when the output tile grid cannot fill 256 CUs but K is deep (conv
 // wgrad: M=Cout, N=Kcol, K=N*OH*OW up to ~800k). 2 blocks/CU resident ->
@@ -370,7 +457,10 @@ inline void ps_generic_plan(const GemmShape& g, GemmPlan* p,
   const bool thin = may_split && tiles < 384;
   // deterministic mode: as if C could not take atomics -- deep-K shapes take
   // the workspace branch below, the rest run unsplit
-  if (thin && g.atomic_ok && !g.deterministic && g.K >= 512) {
+  if (thin && g.skinny_kmin > 0 && !g.atomic_ok && !g.deterministic &&
+      !g.only128 && g.M <= PS_SKINNY_MAX_M) {
+    ps_skinny_plan(g, p);
+  } else if (thin && g.atomic_ok && !g.deterministic && g.K >= 512) {
     // atomic split-K: no workspace, so split much deeper (chunk >= 256)
     // -- the un-split grid leaves most of the 256 CUs idle
     const int64_t a = (512 + tiles - 1) / tiles, b = (g.K + 255) / 256;

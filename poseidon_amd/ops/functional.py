@@ -164,11 +164,32 @@ def fused_weight_tail() -> bool:
 
 
 def gemm_plan(M: int, N: int, K: int, a_klast: bool, b_klast: bool,
-              bf16: bool) -> dict:
+              bf16: bool, out_f32: bool = True, bias: bool = False) -> dict:
     """The launch plan of the test GEMM entry for this shape right now:
-    tr16, splitk, ws_elems, bm, bn, kchunk, grid_z."""
+    tr16, splitk, ws_elems, bm, bn, kchunk, grid_z, skinny.
+    out_f32=False (a C of the input type) and bias=True plan what
+    linear_forward and linear_backward's dx run."""
     return dict(_ext().gemm_plan(int(M), int(N), int(K), bool(a_klast),
-                                 bool(b_klast), bool(bf16)))
+                                 bool(b_klast), bool(bf16), bool(out_f32),
+                                 bool(bias)))
+
+
+def set_skinny_splitk(on: bool, kmin: int = 0, bm: int = 0, bn: int = 0,
+                      splitk: int = 0) -> None:
+    """Toggle the skinny split-K plans: fc forward and data-gradient GEMMs
+    (M <= 512, thin tile grid, a C that cannot take atomics) choose tile and
+    split depth together so that the grid fills the chip; the split is
+    reduced in slice order by the reduce launch, as before. Off plans them as
+    every other workspace split. Never taken in deterministic mode. Default on
+    (docs/performance.md item 31); PS_SKINNY_SPLITK=0/1 sets it at import.
+    kmin (the K-slice floor), bm, bn and splitk are for tests and tuning
+    runs: 0 leaves each to the planner."""
+    _ext().set_skinny_splitk(bool(on), int(kmin), int(bm), int(bn),
+                             int(splitk))
+
+
+def skinny_splitk() -> bool:
+    return bool(_ext().skinny_splitk()) if ext_available() else False
 
 
 def float_atomic_launches(reset: bool = False) -> int:
