@@ -141,6 +141,25 @@ std::atomic<bool> g_packed_conv{false};
 std::atomic<bool> g_rowfused_conv{true};
 std::atomic<int64_t> g_rowfused_thresh{256LL << 20};
 
+// Halo-tile direct conv (ps_halo.h, conv_halo.hip) for thin stride-1 bf16
+// layers (G == 1, Ci % 32 == 0, Co % 16 == 0, Co <= 64, filter bank and two
+// input patches within the LDS): it replaces the gathered GEMM of an implicit
+// forward and of a dgrad-as-forward once the column matrix reaches the
+// threshold, i.e. VGG conv1_2 (2.3 GB) at the default 256 MiB. Weight
+// layouts and the cache sentinel are the gathered path's. The default and
+// the measurements behind it: docs/performance.md item 32.
+// PS_HALO_CONV=0/1 sets the switch at import.
+std::atomic<bool> g_halo_conv{false};
+std::atomic<int64_t> g_halo_thresh{256LL << 20};
+
+void set_halo_conv(bool on) { g_halo_conv.store(on); }
+bool halo_conv() { return g_halo_conv.load(); }
+void set_halo_threshold(int64_t bytes) { g_halo_thresh.store(bytes); }
+int64_t halo_threshold() { return g_halo_thresh.load(); }
+int64_t halo_conv_launches(bool reset) {
+  return ps_halo_launches(reset ? 1 : 0);
+}
+
 void set_rowfused_conv(bool on) { g_rowfused_conv.store(on); }
 bool rowfused_conv() { return g_rowfused_conv.load(); }
 int64_t rowfused_threshold() { return g_rowfused_thresh.load(); }
@@ -411,7 +430,8 @@ ConvPlan conv_plan_for(at::IntArrayRef x_shape, int Co, int kh, int kw,
       packed == PS_PACKED_AUTO ? g_packed_conv.load() : packed == PS_PACKED_ON,
       rf_auto ? g_rowfused_conv.load() : rowfused == PS_ROWFUSED_ON,
       rf_auto ? g_rowfused_thresh.load() : 0,
-      rf_auto && ps_deterministic() != 0};
+      rf_auto && ps_deterministic() != 0,
+      g_halo_conv.load(), g_halo_thresh.load()};
   ConvPlan p = ps_conv_plan((int)x_shape[0], (int)x_shape[1], (int)x_shape[2],
                             (int)x_shape[3], Co, kh, kw, sh, sw, ph, pw, G,
                             bf16 ? 2 : 4, policy);
@@ -419,7 +439,33 @@ ConvPlan conv_plan_for(at::IntArrayRef x_shape, int Co, int kh, int kw,
   // LDS attribute (once per process), never a launch or a captured region;
   // without a usable device the plan keeps the column matrix
   if (p.rowfused && !ps_rowfused_prepare()) p.rowfused = false;
+  // the halo kernel likewise
+  if ((p.halo_fwd || p.halo_dgrad) && !ps_halo_prepare())
+    p.halo_fwd = p.halo_dgrad = false;
   return p;
+}
+
+// One halo-tile launch: out = act(conv(in, w) + bias) for NHWC bf16 in / out
+// (in's shape as NCHW sizes), w K-last khwc rows w_ld apart, pads (ph, pw)
+void run_halo_conv(const Tensor& in, const Tensor& w, int64_t w_ld,
+                   const float* bias, Tensor& out, int Co, int kh, int kw,
+                   int ph, int pw, bool relu) {
+  const HaloTiling t = ps_halo_tiling(
+      (int)in.size(0), (int)in.size(1), (int)in.size(2), (int)in.size(3), Co,
+      kh, kw, 1, 1, ph, pw, 1, 2, ps_halo_max_blocks());
+  TORCH_CHECK(t.ok && is_bf16(in) && is_bf16(w) && is_bf16(out),
+              "halo conv: shape or dtype outside the plan");
+  TORCH_CHECK(out.size(1) == Co && out.size(2) == t.Ho && out.size(3) == t.Wo,
+              "halo conv: output shape mismatch");
+  TORCH_CHECK(w.is_contiguous() && w_ld % 8 == 0 && w.size(0) >= Co &&
+              w.size(1) >= t.K && w.size(1) == w_ld,
+              "halo conv: weight rows");
+  TORCH_CHECK(((uintptr_t)in.data_ptr() & 15) == 0 &&
+              ((uintptr_t)w.data_ptr() & 15) == 0 &&
+              ((uintptr_t)out.data_ptr() & 15) == 0,
+              "halo conv: operands must be 16 B aligned");
+  ps_conv_halo(&t, in.data_ptr(), w.data_ptr(), w_ld, bias, out.data_ptr(),
+               relu ? 1 : 0, stream());
 }
 
 // the plan as Python sees it (Net sizes its persistent wk buffers from it)
@@ -444,6 +490,7 @@ py::dict conv_plan(std::vector<int64_t> x_shape, std::vector<int64_t> w_shape,
   d["packed"] = p.packed; d["pk_W"] = p.pk_W; d["pk_kw"] = p.pk_kw;
   d["pk_Kg"] = p.pk_Kg; d["kw_ld"] = p.kw_ld; d["c_ld"] = p.c_ld;
   d["rowfused"] = p.rowfused;
+  d["halo_fwd"] = p.halo_fwd; d["halo_dgrad"] = p.halo_dgrad;
   // width of the khwc wgrad scratch
   d["Kgw"] = p.implicit ? p.Kgw_implicit : p.wk_ld;
   return d;
@@ -574,6 +621,13 @@ std::vector<Tensor> conv2d_forward_ex(const Tensor& x, const Tensor& w,
   // per-group K incl. pad: wk rows are PADDED to wk_ld, so the implicit
   // GEMM runs over the padded K too (gather k >= kg_max reads the zero
   // page, wk pad cols are zero)
+  if (p.halo_fwd) {
+    // in place of the gathered GEMM below; the wgrad sees the same implicit
+    // sentinel
+    run_halo_conv(x_cl, wk, p.wk_ld, bp, y, Co, g.kh, g.kw, g.ph, g.pw,
+                  fuse_relu);
+    return {y, at::empty({0}, x.options()), wkT};
+  }
   const int Kgl = p.wk_ld;
   const bool gather = p.implicit || p.packed;
   const Tensor& xg = p.packed ? colT : x_cl;  // what the gather reads
@@ -617,6 +671,11 @@ Tensor conv2d_backward_input(const Tensor& w, const Tensor& dy,
     Tensor wr = at::empty({(int64_t)G * Cg, (int64_t)K2}, dy.options());
     PS_CALL_W(weight_to_dgrad, bf16, wc.data_ptr<float>(), P(wr), Co, Cg,
             g.kh, g.kw, G, stream());
+    if (p.halo_dgrad) {
+      run_halo_conv(dy_cl, wr, K2, nullptr, dx, Cg, g.kh, g.kw,
+                    g.kh - 1 - g.ph, g.kw - 1 - g.pw, false);
+      return dx;
+    }
     int64_t NP2 = (int64_t)g.N * g.H * g.W;
     for (int grp = 0; grp < G; ++grp) {
       GatherDesc ga = ps_gather_desc(p, PS_GATHER_DGRAD_AS_FWD,
@@ -1880,6 +1939,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("rowfused_threshold", &rowfused_threshold);
   // tests only: cap on the row-fused kernels' persistent grid (0 = auto)
   m.def("set_rowfused_blocks", &ps_rowfused_set_blocks);
+  m.def("set_halo_conv", &set_halo_conv);
+  m.def("halo_conv", &halo_conv);
+  m.def("set_halo_threshold", &set_halo_threshold);
+  m.def("halo_threshold", &halo_threshold);
+  m.def("halo_conv_launches", &halo_conv_launches);
+  // tests only: cap on the halo kernel's persistent grid (0 = CU count)
+  m.def("set_halo_blocks", &ps_halo_set_blocks);
+  if (const char* e = std::getenv("PS_HALO_CONV"))
+    set_halo_conv(std::atoi(e) != 0);
   if (const char* e = std::getenv("PS_ROWFUSED_CONV"))
     set_rowfused_conv(std::atoi(e) != 0);
   m.def("set_dgrad_fwd_threshold", &set_dgrad_fwd_threshold);

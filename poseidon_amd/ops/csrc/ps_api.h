@@ -262,6 +262,22 @@ int ps_rowfused_prepare();
 // tests only: cap on the persistent grid (0 = one block per CU)
 void ps_rowfused_set_blocks(int n);
 
+// conv_halo.hip: halo-tile direct conv (ps_halo.h), bf16 NHWC in and out,
+// stride 1. w is K-last khwc rows w_ld elements apart: the forward's wk or
+// the dgrad-as-forward's wr (in = dy, pads k - 1 - p, no bias, no relu).
+void ps_conv_halo(const HaloTiling*, const void* in, const void* w,
+                  int64_t w_ld, const float* bias, void* out, int relu,
+                  hipStream_t);
+// once per process, when a plan comes out halo: reads the CU count and sets
+// the kernels' LDS attribute; 0 = no usable device
+int ps_halo_prepare();
+// persistent grid size for ps_halo_tiling: the tests' cap, else the CU count
+int ps_halo_max_blocks();
+// tests only: cap on the persistent grid (0 = one block per CU)
+void ps_halo_set_blocks(int n);
+// host-side count of ps_conv_halo launches
+int64_t ps_halo_launches(int reset);
+
 // im2col.hip
 void ps_chan_concat4_f32(float*, void* const*, const int*, int, int, int64_t,
                          int, int, const void* const*, hipStream_t);

@@ -5,6 +5,7 @@
 #pragma once
 #include <cstdint>
 
+#include "ps_halo.h"
 #include "ps_rowfused.h"
 
 #if defined(__HIPCC__)
@@ -54,6 +55,12 @@ struct ConvPolicy {
   bool rowfused;
   int64_t rowfused_bytes;
   bool deterministic;
+  // halo-tile direct conv for thin stride-1 layers (ps_halo.h): switch, and
+  // the column-matrix size from which an implicit forward / a
+  // dgrad-as-forward takes it. Appended: programs that brace-initialise the
+  // fields above leave the path off.
+  bool halo;
+  int64_t halo_bytes;
 };
 
 // Packed first-layer layout (G==1, C <= 4, even sw): x is copied once into
@@ -121,6 +128,10 @@ struct ConvPlan {
   // staged input rows (conv_rowfused.hip); no column matrix. The layouts
   // (ld_col, wk_ld, khwc order) are the materialized path's.
   bool rowfused;
+  // halo-tile direct conv (conv_halo.hip) in place of the gathered GEMM of an
+  // implicit forward / of a dgrad-as-forward. Operands, weight layouts and
+  // the implicit cache sentinel are the gathered path's.
+  bool halo_fwd, halo_dgrad;
 };
 
 inline ConvPlan ps_conv_plan(int N, int C, int H, int W, int Co, int kh,
@@ -171,6 +182,14 @@ inline ConvPlan ps_conv_plan(int N, int C, int H, int W, int Co, int kh,
   p.dgrad_as_fwd = sh == 1 && sw == 1 && !p.is_1x1 && p.Cog % p.vec == 0 &&
                    ph <= kh - 1 && pw <= kw - 1 &&
                    colT_bytes > policy.dgrad_fwd_bytes;
+  const bool halo = policy.halo && colT_bytes >= policy.halo_bytes;
+  p.halo_fwd = halo && p.implicit &&
+               ps_halo_tiling(N, C, H, W, Co, kh, kw, sh, sw, ph, pw, G,
+                              elem_bytes, 1).ok;
+  // the dgrad convolves dy (Co channels, Ho x Wo) into dx with pads k - 1 - p
+  p.halo_dgrad = halo && p.dgrad_as_fwd &&
+                 ps_halo_tiling(N, Co, p.g.Ho, p.g.Wo, C, kh, kw, sh, sw,
+                                kh - 1 - ph, kw - 1 - pw, G, elem_bytes, 1).ok;
   return p;
 }
 

@@ -109,6 +109,52 @@ def _set_rowfused_blocks(n: int) -> None:
         _ext().set_rowfused_blocks(int(n))
 
 
+HALO_THRESHOLD_DEFAULT = 256 << 20
+
+
+def set_halo_conv(on: bool) -> None:
+    """Toggle the halo-tile direct conv (conv_halo.hip) for thin stride-1
+    bf16 layers (groups == 1, Ci % 32 == 0, Co % 16 == 0, Co <= 64, kernels
+    up to 5x5): filter bank resident in LDS, each input patch staged once for
+    all taps. It replaces the gathered GEMM of an implicit-GEMM forward and of
+    a dgrad-as-forward whose column matrix reaches set_halo_threshold (VGG
+    conv1_2 at the default). Weight layouts and persistent buffers are the
+    gathered path's; it has no atomics, so deterministic mode may use it.
+    Default off (docs/performance.md item 32); the environment variable
+    PS_HALO_CONV=0/1 sets it at import."""
+    if ext_available():
+        _ext().set_halo_conv(bool(on))
+
+
+def halo_conv() -> bool:
+    return bool(_ext().halo_conv()) if ext_available() else False
+
+
+def set_halo_threshold(bytes_: int) -> None:
+    """Column-matrix size from which an eligible conv takes the halo path."""
+    if ext_available():
+        _ext().set_halo_threshold(int(bytes_))
+
+
+def halo_threshold() -> int:
+    return (int(_ext().halo_threshold()) if ext_available()
+            else HALO_THRESHOLD_DEFAULT)
+
+
+def _set_halo_blocks(n: int) -> None:
+    """Tests only: cap on the halo kernel's persistent grid (0 = one block
+    per CU), so that a small case walks several tiles per block."""
+    if ext_available():
+        _ext().set_halo_blocks(int(n))
+
+
+def halo_conv_launches(reset: bool = False) -> int:
+    """Launches so far of the halo-tile conv kernel (a host-side counter)."""
+    if not ext_available():
+        return 0
+    return int(_ext().halo_conv_launches(bool(reset)))
+
+
 def conv_policy_epoch() -> int:
     return _conv_policy_epoch
 
@@ -855,7 +901,7 @@ def sgd_mt_run(mt, lr: float, momentum: float, lr_dev=None) -> None:
 def conv_plan(x_shape, w_shape, stride, pad, groups: int, bf16: bool) -> dict:
     """The conv layout plan the bindings derive for this problem (column
     stride ld_col, padded weight width wk_ld, implicit / dgrad-as-forward
-    choices, ...) under the current implicit-GEMM policy."""
+    choices, halo_fwd / halo_dgrad, ...) under the current policy."""
     return _ext().conv_plan(list(x_shape), list(w_shape), list(stride),
                             list(pad), int(groups), bool(bf16))
 

@@ -27,6 +27,7 @@ sources = [
         "sgd.hip",
         "im2col.hip",
         "conv_rowfused.hip",
+        "conv_halo.hip",
         "transform.hip",
         "stats.hip",
     ]
