@@ -39,6 +39,11 @@ class _Context:
     deterministic: bool = field(
         default_factory=lambda: os.environ.get("PS_DETERMINISTIC", "0")
         not in ("", "0"))
+    # fp32 GEMMs through the bf16x3 split kernel (ops.set_fp32_split); off by
+    # default, PS_FP32_SPLIT=1 turns it on at import
+    fp32_split: bool = field(
+        default_factory=lambda: os.environ.get("PS_FP32_SPLIT", "0")
+        not in ("", "0"))
     phase_stack: list = field(default_factory=list)
 
     @property
@@ -62,7 +67,8 @@ def init(device: Optional[str] = None, rank: Optional[int] = None,
          world_size: Optional[int] = None, seed: Optional[int] = None,
          compute_dtype: Optional[torch.dtype] = None,
          device_transform: Optional[bool] = None,
-         deterministic: Optional[bool] = None) -> _Context:
+         deterministic: Optional[bool] = None,
+         fp32_split: Optional[bool] = None) -> _Context:
     """(Re)configure the global context. Reads torchrun env vars when args
     are omitted."""
     if rank is None:
@@ -92,4 +98,8 @@ def init(device: Optional[str] = None, rank: Optional[int] = None,
         from ..ops import functional as ops
         ops.set_deterministic(bool(deterministic))
         _ctx.deterministic = bool(deterministic)
+    if fp32_split is not None:
+        from ..ops import functional as ops
+        ops.set_fp32_split(bool(fp32_split))
+        _ctx.fp32_split = bool(fp32_split)
     return _ctx

@@ -179,6 +179,14 @@ int64_t float_atomic_launches(bool reset) {
   return ps_float_atomic_launches(reset ? 1 : 0);
 }
 
+// Split-precision fp32 GEMMs (ps_api.h, gemm_split.hip): the switch lives
+// with the kernel, initially PS_FP32_SPLIT=1; planning reads it.
+bool fp32_split() { return ps_fp32_split() != 0; }
+void set_fp32_split(bool on) { ps_set_fp32_split(on ? 1 : 0); }
+int64_t fp32_split_launches(bool reset) {
+  return ps_fp32_split_launches(reset ? 1 : 0);
+}
+
 // out[c] += column sums of d[R][C] (out: f32 [C] on d's device)
 void colsum_into(const Tensor& d, float* out, int64_t R, int C) {
   Tensor scratch;  // deterministic mode: [blocks][C] partials
@@ -286,6 +294,7 @@ py::dict gemm_plan(int M, int N, int K, bool a_klast, bool b_klast,
   py::dict d;
   d["skinny"] = p.skinny;
   d["tr16"] = p.tr16;
+  d["split3"] = p.split3;
   d["splitk"] = p.splitk;
   d["ws_elems"] = p.ws_elems;
   d["bm"] = p.bm;
@@ -1924,6 +1933,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("set_deterministic", &set_deterministic);
   m.def("deterministic", &deterministic);
   m.def("float_atomic_launches", &float_atomic_launches);
+  m.def("set_fp32_split", &set_fp32_split);
+  m.def("fp32_split", &fp32_split);
+  m.def("fp32_split_launches", &fp32_split_launches);
   // tests / tuning: force the tr16 TN tile and its split-K block target
   // (all 0 = the planner's choice)
   m.def("set_tr16_tune", &ps_gemm_set_tr_tune);

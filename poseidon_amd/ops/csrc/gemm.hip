@@ -49,6 +49,7 @@
 #include "ps_common.h"
 #include "ps_api.h"
 #include "ps_gather.h"
+#include "ps_gemm_device.h"  // gather_addr, gemm_epilogue, splitk_reduce_k
 
 namespace ps {
 
@@ -85,20 +86,6 @@ template <> struct GemmTraits<__bf16> {
     return *reinterpret_cast<const frag_t*>(&lds_row[kk + (lane >> 4) * 8]);
   }
 };
-
-// Implicit-GEMM address: row = im2col row (n,oh,ow), k = column within the
-// group slice (khw*Cg + cg). Returns the NHWC x address of k's element run
-// (contiguous along cg), or the zero page for padding. Valid for vector
-// loads that stay inside one cg-run (callers guarantee k%VEC==0, Cg%VEC==0).
-// The integer logic lives in ps_gather.h.
-template <typename T>
-__device__ inline const T* gather_addr(const GatherDesc& ga, int64_t row, int k) {
-  if (k >= ga.kg_max) return (const T*)ga.zero;  // padded columns
-  const GatherRow r = ps_gather_row(ga, (int)row);
-  const GatherTap t = ps_gather_tap(ga, k);
-  if (ps_gather_oob(ga, r, t, k)) return (const T*)ga.zero;
-  return (const T*)ga.x + ps_gather_offset(r, t);
-}
 
 // Direct global->LDS staging (glds): each wave-instruction moves 1 KiB
 // (64 lanes x 16 B) HBM -> LDS without a VGPR round trip
@@ -521,50 +508,6 @@ __device__ inline void mainloop_glds(const T* A, const T* B, int64_t lda,
   }
 }
 
-// Epilogue: C/D fragment map for 16x16 shapes: col = lane&15,
-// row = (lane>>4)*4 + r (guide §3; dtype-independent on gfx950).
-// bz is the split-K slice (the workspace slab it writes).
-template <typename OUT, int FM, int FN, bool HAS_BIAS, bool SPLITK>
-__device__ inline void gemm_epilogue(const f32x4 (&acc)[FM][FN],
-                                     OUT* __restrict__ C,
-                                     const float* __restrict__ bias,
-                                     float* __restrict__ ws, int M, int N,
-                                     int64_t ldc, float alpha, float beta,
-                                     bool relu, int bz, int m0, int n0,
-                                     int wm, int wn, int lane) {
-#pragma unroll
-  for (int fm = 0; fm < FM; ++fm) {
-#pragma unroll
-    for (int fn = 0; fn < FN; ++fn) {
-      int col = n0 + wn + fn * 16 + (lane & 15);
-      if (col >= N) continue;
-      float bv = HAS_BIAS ? bias[col] : 0.0f;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        int row = m0 + wm + fm * 16 + (lane >> 4) * 4 + r;
-        if (row >= M) continue;
-        if (SPLITK) {
-          if (ws) {
-            // raw partial; alpha/beta/bias applied by the reduce kernel
-            ws[((int64_t)bz * M + row) * N + col] = acc[fm][fn][r];
-          } else if constexpr (std::is_same<OUT, float>::value) {
-            // atomic split-K: accumulate straight into zeroed f32 C --
-            // no workspace round-trip, no reduce kernel; lets the launcher
-            // split K much deeper (wgrad tiles are tiny: M=Cout)
-            atomicAdd(&C[(int64_t)row * ldc + col], alpha * acc[fm][fn][r]);
-          }
-        } else {
-          int64_t idx = (int64_t)row * ldc + col;
-          float v = alpha * acc[fm][fn][r] + bv;
-          if (beta != 0.0f) v += beta * to_f32(C[idx]);
-          if (relu && v < 0.0f) v = 0.0f;  // fused in-place ReLU epilogue
-          from_f32(v, C[idx]);
-        }
-      }
-    }
-  }
-}
-
 // xcd2d: the plan's 2D-XCD rectangle as (ry << 16) | cx, 0 for none
 template <typename T, typename OUT, int BM, int BN, int WGM, int WGN,
           bool A_KLAST, bool B_KLAST, bool HAS_BIAS, bool SPLITK,
@@ -672,28 +615,6 @@ void gemm_kernel(const T* __restrict__ A, const T* __restrict__ B,
   gemm_epilogue<OUT, FM, FN, HAS_BIAS, SPLITK>(acc, C, bias, ws, M, N, ldc,
                                                alpha, beta, relu, blk.bz, m0,
                                                n0, wm, wn, lane);
-}
-
-// combine split-K partial slabs: C = alpha*sum_s ws[s] + bias + beta*C
-template <typename OUT, bool HAS_BIAS>
-__global__ void splitk_reduce_k(const float* __restrict__ ws,
-                                OUT* __restrict__ C,
-                                const float* __restrict__ bias,
-                                int M, int N, int64_t ldc, int splitk,
-                                float alpha, float beta, bool relu) {
-  int64_t MN = (int64_t)M * N;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < MN;
-       i += (int64_t)gridDim.x * blockDim.x) {
-    float v = 0.f;
-    for (int s = 0; s < splitk; ++s) v += ws[s * MN + i];
-    int row = i / N, col = i % N;
-    v *= alpha;
-    if (HAS_BIAS) v += bias[col];
-    int64_t idx = (int64_t)row * ldc + col;
-    if (beta != 0.0f) v += beta * to_f32(C[idx]);
-    if (relu && v < 0.0f) v = 0.0f;
-    from_f32(v, C[idx]);
-  }
 }
 
 
@@ -1239,7 +1160,8 @@ static void run_gemm_generic(const GemmArgs& g, const GemmPlan& p, float* ws,
     float_atomic_launch("gemm split-K");
     zero_c_for_atomics(g, s);
   }
-  if (!g.in_bf16) gemm_dispatch<float, float>(g, p, ws, s);
+  if (p.split3) ps_gemm_split_run(&g, &p, ws, s);  // gemm_split.hip
+  else if (!g.in_bf16) gemm_dispatch<float, float>(g, p, ws, s);
   else if (g.out_f32) gemm_dispatch<__bf16, float>(g, p, ws, s);
   else gemm_dispatch<__bf16, __bf16>(g, p, ws, s);
 }
@@ -1325,9 +1247,20 @@ static void run_gemm_tn_tr(const GemmArgs& g, const GemmPlan& p, float* ws,
 extern "C" {
 
 // tr16 plan first (bf16 in, fp32 out only), else the generic plan
+// Split-precision fp32 (gemm_split.hip), when switched on: fp32 operands in
+// one of the three layouts training reaches and at least one staged tile of
+// K. Planned like any fp32 GEMM, on its own staged K tile and without the
+// N-fitting tiles, which it is not built for.
 void ps_gemm_plan(const GemmArgs* g, GemmPlan* plan) {
-  const GemmShape sh = gemm_shape(*g);
+  GemmShape sh = gemm_shape(*g);
+  const bool split3 = ps_fp32_split() && !g->in_bf16 &&
+                      (g->a_klast || !g->b_klast) && g->K >= PS_SPLIT3_BK;
+  if (split3) {
+    sh.bk = PS_SPLIT3_BK;
+    sh.nt = false;
+  }
   if (!ps_tn_tr_plan(sh, g_tr_tune, plan)) ps_generic_plan(sh, plan);
+  plan->split3 = split3 && !plan->tr16;
 }
 
 void ps_set_deterministic(int on) { g_deterministic.store(on ? 1 : 0); }

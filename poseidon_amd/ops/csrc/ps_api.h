@@ -29,6 +29,9 @@ struct GemmArgs {
   bool c_prezeroed;
 };
 
+// fp32 K elements per staged tile of the split-precision kernel
+constexpr int PS_SPLIT3_BK = 32;
+
 struct PoolGeom {
   int N, C, H, W, Ho, Wo;
   int kh, kw, sh, sw, ph, pw;
@@ -56,6 +59,19 @@ int ps_deterministic();
 // atomically (LDS or global): each launcher calls ps_count_float_atomic.
 void ps_count_float_atomic();
 int64_t ps_float_atomic_launches(int reset);
+
+// gemm_split.hip: split-precision fp32 GEMMs. Each fp32 operand is staged as
+// two bf16 images hi + lo and a product is three bf16 MFMAs (lo*hi + hi*lo +
+// hi*hi) into the fp32 accumulator. The switch is process-wide (initially
+// PS_FP32_SPLIT=1, default off); ps_gemm_plan reads it and marks the plans
+// that ps_gemm_run then sends to ps_gemm_split_run.
+void ps_set_fp32_split(int on);
+int ps_fp32_split();
+// host-side count of ps_gemm_split_run launches
+int64_t ps_fp32_split_launches(int reset);
+// a generic plan with split3 set; split-K zeroing / workspace as ps_gemm_run
+void ps_gemm_split_run(const GemmArgs* g, const GemmPlan* plan, float* ws,
+                       hipStream_t s);
 
 // elementwise.hip
 void ps_relu_fwd_f32(const float*, float*, int64_t, float, hipStream_t);

@@ -26,6 +26,7 @@ struct GemmPlan {
   int M0, N0;        // tr16 only: interior extent (edge strips run generic)
   int ry, cx;        // generic only: 2D-XCD rectangle in tiles (0: none)
   bool skinny;       // generic only: made by ps_skinny_plan (for reporting)
+  bool split3;       // generic only: fp32 in, run by the bf16x3 split kernel
 };
 
 // Manual override of the skinny plan's tile and depth, 0 = planner's choice.

@@ -191,6 +191,50 @@ def deterministic() -> bool:
     return _deterministic_cpu
 
 
+# Split-precision fp32. The switch lives in the extension (one per process,
+# initially PS_FP32_SPLIT=1); without the extension it is a no-op that
+# remembers its value.
+_fp32_split_cpu = os.environ.get("PS_FP32_SPLIT", "0") not in ("", "0")
+
+
+def set_fp32_split(on: bool) -> None:
+    """Opt-in split-precision fp32 GEMMs (gemm_split.hip): every fp32 GEMM
+    of K >= 32 in a layout training reaches -- InnerProduct forward and
+    backward, the conv GEMMs, gathered or not -- stages each operand as two
+    bf16 images hi + lo and runs three bf16 MFMAs per product (lo*hi + hi*lo
+    + hi*hi) into the fp32 accumulator instead of the exact fp32 MFMA.
+    Element-wise |got - exact| <= (2^-16 + K * 2^-22) * sum_k |a_k| |b_k|;
+    non-finite operands give non-finite results of an undefined kind
+    (docs/architecture.md). Blobs, solver state and snapshots stay fp32;
+    bf16 compute and every non-GEMM kernel are unaffected. Default off; the
+    environment variable PS_FP32_SPLIT=0/1 sets it at import. Toggling bumps
+    conv_policy_epoch() so nets re-plan their cached tables."""
+    global _fp32_split_cpu, _conv_policy_epoch
+    on = bool(on)
+    if on == fp32_split():
+        return
+    if ext_available():
+        _ext().set_fp32_split(on)
+    _fp32_split_cpu = on
+    _conv_policy_epoch += 1
+    from ..core.context import ctx
+    ctx().fp32_split = on
+
+
+def fp32_split() -> bool:
+    if ext_available():
+        return bool(_ext().fp32_split())
+    return _fp32_split_cpu
+
+
+def fp32_split_launches(reset: bool = False) -> int:
+    """Launches so far of the split-precision GEMM kernel (a host-side
+    counter). reset=True also sets it back to zero."""
+    if not ext_available():
+        return 0
+    return int(_ext().fp32_split_launches(bool(reset)))
+
+
 # The fused weight tail (docs/architecture.md): fc weight gradients are
 # written straight into the param diff, sole-owner diffs leave the zero
 # table, and the SGD kernel writes the fc bf16 shadows. Off reproduces the
@@ -212,7 +256,7 @@ def fused_weight_tail() -> bool:
 def gemm_plan(M: int, N: int, K: int, a_klast: bool, b_klast: bool,
               bf16: bool, out_f32: bool = True, bias: bool = False) -> dict:
     """The launch plan of the test GEMM entry for this shape right now:
-    tr16, splitk, ws_elems, bm, bn, kchunk, grid_z, skinny.
+    tr16, split3, splitk, ws_elems, bm, bn, kchunk, grid_z, skinny.
     out_f32=False (a C of the input type) and bias=True plan what
     linear_forward and linear_backward's dx run."""
     return dict(_ext().gemm_plan(int(M), int(N), int(K), bool(a_klast),

@@ -2,7 +2,11 @@
 rules 24/25). Usage:
 
     python -m poseidon_amd.tools.gemm_bench [--size 4096] [--dtype bf16]
-        [--layout nt|nn|tn] [--reps 20]
+        [--layout nt|nn|tn] [--reps 20] [--split]
+
+--split (fp32 only) times the exact fp32 path and then the split-precision
+path (ops.set_fp32_split) in the same process after one clock ramp, and
+prints both with their ratio; TF/s is effective, from the fp32 FLOP count.
 """
 
 import argparse
@@ -18,7 +22,11 @@ def main(argv=None):
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp32"])
     ap.add_argument("--layout", default="nt", choices=["nt", "nn", "tn"])
     ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--split", action="store_true",
+                    help="also time the bf16x3 split path (needs --dtype fp32)")
     args = ap.parse_args(argv)
+    if args.split and args.dtype != "fp32":
+        ap.error("--split is valid with --dtype fp32 only")
 
     from poseidon_amd.ops._backend import load
     ext = load()
@@ -36,26 +44,40 @@ def main(argv=None):
     A = (opA if ak else opA.t()).contiguous().to("cuda", dt)
     B = (opB.t() if bk else opB).contiguous().to("cuda", dt)
 
-    # correctness spot-check FIRST: the CPU reference matmul takes seconds,
-    # and any GPU-idle gap right before the timed region lets DVFS drop the
-    # clocks for the whole measurement (guide rule 24; measured 50x once)
-    out = ext.gemm(A, B, M, N, K, ak, bk)
-    ref = (opA.to(dt).float() @ opB.to(dt).float())
-    err = (out.cpu() - ref).abs().max().item()
-    # clock ramp: keep the GPU busy ~100 ms right before timing
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    while time.perf_counter() - t0 < 0.1:
-        ext.gemm(A, B, M, N, K, ak, bk)
+    def measure(split):
+        # correctness spot-check FIRST: the CPU reference matmul takes
+        # seconds, and any GPU-idle gap right before the timed region lets
+        # DVFS drop the clocks for the whole measurement (guide rule 24;
+        # measured 50x once)
+        if args.split:
+            ext.set_fp32_split(split)
+        out = ext.gemm(A, B, M, N, K, ak, bk)
+        err = (out.cpu() - ref).abs().max().item()
+        # clock ramp: keep the GPU busy ~100 ms right before timing
         torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for _ in range(args.reps):
-        ext.gemm(A, B, M, N, K, ak, bk)
-    torch.cuda.synchronize()
-    dt_s = (time.perf_counter() - t0) / args.reps
-    tf = 2.0 * M * N * K / dt_s / 1e12
-    print(f"{args.layout} {args.dtype} {M}x{N}x{K}: {tf:.1f} TF/s "
-          f"({dt_s * 1e3:.3f} ms), max_err={err:.3g}")
+        t0 = time.perf_counter()
+        while time.perf_counter() - t0 < 0.1:
+            ext.gemm(A, B, M, N, K, ak, bk)
+            torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(args.reps):
+            ext.gemm(A, B, M, N, K, ak, bk)
+        torch.cuda.synchronize()
+        dt_s = (time.perf_counter() - t0) / args.reps
+        tf = 2.0 * M * N * K / dt_s / 1e12
+        name = args.dtype + (" split" if split else "")
+        print(f"{args.layout} {name} {M}x{N}x{K}: {tf:.1f} TF/s "
+              f"({dt_s * 1e3:.3f} ms), max_err={err:.3g}")
+        return dt_s
+
+    ref = (opA.to(dt).float() @ opB.to(dt).float())
+    was = ext.fp32_split()
+    try:
+        exact = measure(False)
+        if args.split:
+            print(f"split / exact speed: {exact / measure(True):.2f}x")
+    finally:
+        ext.set_fp32_split(was)
 
 
 if __name__ == "__main__":

@@ -21,6 +21,9 @@ def main(argv=None):
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp32"])
     ap.add_argument("--stats", default="", help="also dump YAML here")
+    ap.add_argument("--fp32-split", action="store_true",
+                    help="with --dtype fp32: split-precision GEMMs, three "
+                         "bf16 MFMAs per product (default off)")
     args = ap.parse_args(argv)
 
     import poseidon_amd as pa
@@ -31,7 +34,8 @@ def main(argv=None):
 
     use_gpu = torch.cuda.is_available()
     cd = torch.bfloat16 if (args.dtype == "bf16" and use_gpu) else torch.float32
-    pa.init(device="cuda" if use_gpu else "cpu", seed=1, compute_dtype=cd)
+    pa.init(device="cuda" if use_gpu else "cpu", seed=1, compute_dtype=cd,
+            fp32_split=True if args.fp32_split else None)
 
     if args.model:
         kw = {"batch": args.batch} if args.batch else {}

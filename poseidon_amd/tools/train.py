@@ -46,6 +46,11 @@ def main(argv=None):
                          "same seed gives the same bits on one GPU in one "
                          "build (default off; PS_DETERMINISTIC=1 does the "
                          "same; costs speed, see docs/performance.md)")
+    ap.add_argument("--fp32-split", action="store_true",
+                    help="with --dtype fp32: run the GEMMs as three bf16 "
+                         "MFMAs per product on hi + lo splits of the fp32 "
+                         "operands (default off; PS_FP32_SPLIT=1 does the "
+                         "same; error bound in docs/architecture.md)")
     ap.add_argument("--graph", action="store_true",
                     help="replay the training iteration from a hipGraph "
                          "(DB-backed data layers need --device-transform); "
@@ -74,7 +79,8 @@ def main(argv=None):
             seed=seed if seed >= 0 else 1,
             compute_dtype=cd,
             device_transform=True if args.device_transform else None,
-            deterministic=True if args.deterministic else None)
+            deterministic=True if args.deterministic else None,
+            fp32_split=True if args.fp32_split else None)
 
     solver = get_solver(solver_param, use_sfb=args.svb)
     if args.weights:

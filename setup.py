@@ -19,6 +19,7 @@ sources = [
     for f in [
         "bindings.cpp",
         "gemm.hip",
+        "gemm_split.hip",
         "elementwise.hip",
         "pool.hip",
         "lrn.hip",
