@@ -204,6 +204,12 @@ const void* zero_page(const Tensor& like) {
   return z.data_ptr();
 }
 
+// tr16 K-tail (ps_api.h): the switch lives with the kernel, initially
+// PS_TR16_KTAIL; planning reads it. Default and measurements:
+// docs/performance.md item 34.
+bool tr16_ktail() { return ps_tr16_ktail() != 0; }
+void set_tr16_ktail(bool on) { ps_set_tr16_ktail(on ? 1 : 0); }
+
 // Skinny split-K plans (ps_gemm_plan.h): fc forward and data-gradient GEMMs
 // at batch-sized M choose tile and split depth together so that the grid
 // fills the chip. Default ON: see docs/performance.md item 31.
@@ -242,6 +248,8 @@ void run_gemm(const Tensor& A, const Tensor& B, Tensor& C,
   g.gather_b = gather_b;
   g.relu = relu;
   g.c_prezeroed = c_prezeroed;
+  // the tr16 K-tail's zero page (a gathered B carries its own)
+  g.zero = g.in_bf16 && K % 64 && tr16_ktail() ? zero_page(A) : nullptr;
   GemmPlan plan;
   ps_gemm_plan(&g, &plan);
   TORCH_CHECK(!deterministic() || plan.splitk == 1 || plan.ws_elems > 0,
@@ -1939,6 +1947,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   // tests / tuning: force the tr16 TN tile and its split-K block target
   // (all 0 = the planner's choice)
   m.def("set_tr16_tune", &ps_gemm_set_tr_tune);
+  m.def("set_tr16_ktail", &set_tr16_ktail);
+  m.def("tr16_ktail", &tr16_ktail);
   m.def("set_implicit_threshold", &set_implicit_threshold);
   m.def("set_packed_conv", &set_packed_conv);
   m.def("khwc_layout", &khwc_layout);

@@ -650,14 +650,21 @@ __device__ inline int tr_swz(int row, int chunk) {
   return chunk ^ (p & MASK);
 }
 
-template <int COLS, bool GATHER = false, bool NT = false>
+template <int COLS, bool GATHER = false, bool NT = false, bool TAIL = false>
 __device__ inline void stage_kmaj_tr(__bf16* lds, const __bf16* src,
                                      int64_t ld, int k0, int c0, int wid,
                                      int lane,
-                                     const GatherDesc* ga = nullptr) {
+                                     const GatherDesc* ga = nullptr,
+                                     int krows = 64,
+                                     const void* zero = nullptr) {
   // [BK=64 rows][COLS cols]: COLS*2 B rows, 16 B lane chunks. GATHER:
   // the operand is the im2col matrix gathered on the fly from NHWC x
   // (row = im2col row np, col = kg) -- implicit wgrad without a colT.
+  // TAIL: the last tile of a K % 64 != 0 contraction. Only its first krows
+  // rows exist; a lane of a later row never forms an operand address and
+  // loads 16 B of the zero page instead, so the image is whole and the MFMA
+  // loop runs it like any other (stale LDS could hold NaN, and 0 * NaN is
+  // NaN: both operands are zeroed, not one).
   constexpr int LPR = COLS / 8;       // lanes per row
   constexpr int RPC = 64 / LPR;       // rows per 1 KB chunk
   constexpr int CHUNKS = 64 / RPC;
@@ -692,8 +699,11 @@ __device__ inline void stage_kmaj_tr(__bf16* lds, const __bf16* src,
                : (const __bf16*)ga->x +
                      (((int64_t)n2 * ga->H + ih) * ga->W + iw) * ga->C +
                      ga->c0 + cg[pi];
+      // a dead row decodes to an image at or past the batch
+      if (TAIL && row >= krows) g2 = (const __bf16*)ga->zero;
     } else {
       g2 = src + (int64_t)(k0 + row) * ld + c0 + sslot * 8;
+      if (TAIL && row >= krows) g2 = (const __bf16*)zero;
     }
     // NT (aux=2): the B stream is read by exactly ONE block; keep it from
     // evicting the XCD-L2-resident A slice the clustered tiles share
@@ -748,23 +758,27 @@ __device__ inline void tr_wait(bf16x8 (&a)[NA], bf16x8 (&b)[NB]) {
 // 32x128 / 64x128 tiles against 0.0 on 64x64), which 128 B rows do not have.
 // A sub-image that starts at or past cmax (ragged last N tile,
 // ps_tr_sub_live) is not staged at all: only dead waves would read it.
-template <int W, bool GATHER = false, bool NT = false>
+template <int W, bool GATHER = false, bool NT = false, bool TAIL = false>
 __device__ inline void stage_panel_tr(__bf16* lds, const __bf16* src,
                                       int64_t ld, int k0, int c0, int cmax,
                                       int wid, int lane,
-                                      const GatherDesc* ga = nullptr) {
+                                      const GatherDesc* ga = nullptr,
+                                      int krows = 64,
+                                      const void* zero = nullptr) {
   if constexpr (W <= 64) {
-    stage_kmaj_tr<W, GATHER, NT>(lds, src, ld, k0, c0, wid, lane, ga);
+    stage_kmaj_tr<W, GATHER, NT, TAIL>(lds, src, ld, k0, c0, wid, lane, ga,
+                                       krows, zero);
   } else {
 #pragma unroll
     for (int i = 0; i < W / 64; ++i)
       if (ps_tr_sub_live(c0, i, cmax))
-        stage_kmaj_tr<64, GATHER, NT>(lds + i * 64 * 64, src, ld, k0,
-                                      c0 + i * 64, wid, lane, ga);
+        stage_kmaj_tr<64, GATHER, NT, TAIL>(lds + i * 64 * 64, src, ld, k0,
+                                            c0 + i * 64, wid, lane, ga,
+                                            krows, zero);
     if constexpr (W % 64 != 0)
-      stage_kmaj_tr<W % 64, GATHER, NT>(lds + (W / 64) * 64 * 64, src, ld,
-                                        k0, c0 + (W / 64) * 64, wid, lane,
-                                        ga);
+      stage_kmaj_tr<W % 64, GATHER, NT, TAIL>(lds + (W / 64) * 64 * 64, src,
+                                              ld, k0, c0 + (W / 64) * 64,
+                                              wid, lane, ga, krows, zero);
   }
 }
 
@@ -796,8 +810,16 @@ __device__ inline bf16x8 tr_panel_frag(unsigned lds_base, int kk, int cb,
 //               < splitk and columns < N are ever read back.
 enum { TR_NOSPLIT = 0, TR_ATOMIC = 1, TR_WS = 2 };
 
+// KT: K % 64 != 0 (ps_tn_tr_plan with ktail). kchunk stays a multiple of 64,
+// so only the launch's last K slice ends in a tile of fewer than 64 k-rows.
+// That one tile is staged by the TAIL staging -- from the prologue when the
+// slice is nothing but a tail, else from the prefetch of the last full
+// tile's iteration -- with its dead rows read from the zero page
+// (ga_b.zero, which the launcher also fills for a materialized B). Every
+// other tile and the whole MFMA loop are the KT = false code, and a launch
+// with K % 64 == 0 runs the KT = false instantiation.
 template <int BM2, int BN2, int WGM2, int WGN2, int SPLITK,
-          bool GB2 = false>
+          bool GB2 = false, bool KT = false>
 __global__ __launch_bounds__(256)
 void gemm_tn_tr_kernel(const __bf16* __restrict__ A,
                        const __bf16* __restrict__ B, float* __restrict__ C,
@@ -840,13 +862,32 @@ void gemm_tn_tr_kernel(const __bf16* __restrict__ A,
   // im2col that just wrote them; nt measured -4% on AlexNet/GoogLeNet)
   const bool ntb = SPLITK != TR_NOSPLIT && gridDim.y == 1 && !GB2 &&
                    (int64_t)K * N * 2 > (192LL << 20);
-  if (ntb)
-    stage_panel_tr<BN2, GB2, true>(b_lds[0], B, ldB, k_begin, n0, N, wid,
-                                   lane, &ga_b);
-  else
-    stage_panel_tr<BN2, GB2, false>(b_lds[0], B, ldB, k_begin, n0, N, wid,
-                                    lane, &ga_b);
-  stage_panel_tr<BM2>(a_lds[0], A, ldA, k_begin, m0, M, wid, lane);
+  // the tile at k0 when fewer than 64 k-rows are left in the slice
+  auto stage_tail = [&](__bf16* a_dst, __bf16* b_dst, int k0) {
+    if constexpr (KT) {
+      const int krows = k_end - k0;
+      stage_panel_tr<BM2, false, false, true>(a_dst, A, ldA, k0, m0, M, wid,
+                                              lane, nullptr, krows,
+                                              ga_b.zero);
+      if (ntb)
+        stage_panel_tr<BN2, GB2, true, true>(b_dst, B, ldB, k0, n0, N, wid,
+                                             lane, &ga_b, krows, ga_b.zero);
+      else
+        stage_panel_tr<BN2, GB2, false, true>(b_dst, B, ldB, k0, n0, N, wid,
+                                              lane, &ga_b, krows, ga_b.zero);
+    }
+  };
+  if (KT && k_begin + 64 > k_end) {
+    stage_tail(a_lds[0], b_lds[0], k_begin);
+  } else {
+    if (ntb)
+      stage_panel_tr<BN2, GB2, true>(b_lds[0], B, ldB, k_begin, n0, N, wid,
+                                     lane, &ga_b);
+    else
+      stage_panel_tr<BN2, GB2, false>(b_lds[0], B, ldB, k_begin, n0, N, wid,
+                                      lane, &ga_b);
+    stage_panel_tr<BM2>(a_lds[0], A, ldA, k_begin, m0, M, wid, lane);
+  }
   __syncthreads();
   unsigned ab[2], bb[2];
 #pragma unroll
@@ -858,7 +899,9 @@ void gemm_tn_tr_kernel(const __bf16* __restrict__ A,
   }
   int cur = 0;
   for (int k0 = k_begin; k0 < k_end; k0 += 64) {
-    if (k0 + 64 < k_end) {
+    if (KT && k0 + 64 < k_end && k0 + 128 > k_end) {
+      stage_tail(a_lds[cur ^ 1], b_lds[cur ^ 1], k0 + 64);
+    } else if (k0 + 64 < k_end) {
       stage_panel_tr<BM2>(a_lds[cur ^ 1], A, ldA, k0 + 64, m0, M, wid,
                           lane);
       if (ntb)
@@ -986,6 +1029,13 @@ static std::atomic<int> g_skinny_kmin{[] {
 }()};
 static SkinnyTune g_skinny_tune = {0, 0, 0};
 
+// tr16 K-tail switch (ps_set_tr16_ktail): K % 64 != 0 contractions may plan
+// tr16. PS_TR16_KTAIL=0/1 at load.
+static std::atomic<int> g_tr16_ktail{[] {
+  const char* e = getenv("PS_TR16_KTAIL");
+  return e && *e ? (atoi(e) != 0 ? 1 : 0) : PS_TR16_KTAIL_DEFAULT;
+}()};
+
 static GemmShape gemm_shape(const GemmArgs& g) {
   GemmShape sh;
   sh.M = g.M;
@@ -999,6 +1049,7 @@ static GemmShape gemm_shape(const GemmArgs& g) {
   sh.nt = g.a_klast && g.b_klast;
   sh.only128 = !g.a_klast && g.b_klast;
   sh.deterministic = ps_deterministic() != 0;
+  sh.ktail = g_tr16_ktail.load() != 0;
   // the fc forward / data-gradient class: a K-last A. Gathered or not: a
   // conv forward plans the same whether its column matrix exists or not
   // (the two paths give the same bits, tests/test_gpu_gather_gemm.py)
@@ -1194,14 +1245,25 @@ static void run_gemm_tn_tr(const GemmArgs& g, const GemmPlan& p, float* ws,
   // grid.z padded: enables L2 clustering
   dim3 grid((N0 + p.bn - 1) / p.bn, M0 / p.bm, ps_tr_grid_z(p));
   GatherDesc gb = g.gather_b ? *g.gather_b : GatherDesc{};
+  // K-tail: the dead k-rows of the last tile read the zero page, the
+  // gather's own or, for materialized operands, the caller's
+  const bool ktail = g.K % 64 != 0;
+  if (!g.gather_b) gb.zero = g.zero;
+  if (ktail && !gb.zero) {
+    fprintf(stderr, "tr16 gemm: K = %d needs a zero page\n", g.K);
+    abort();
+  }
 #define PS_TR_CASE(BM_, BN_, WGM_, WGN_)                                    \
   if (p.bm == BM_ && p.bn == BN_)                                           \
     with_tr_mode(mode, [&](auto sk) {                                       \
       with_bool(g.gather_b != nullptr, [&](auto gat) {                      \
-        gemm_tn_tr_kernel<BM_, BN_, WGM_, WGN_, decltype(sk)::value,        \
-                          decltype(gat)::value><<<grid, 256, 0, s>>>(       \
-            (const __bf16*)g.A, (const __bf16*)g.B, out, M0, N0,            \
-            g.K, g.lda, g.ldb, g.ldc, g.alpha, p.kchunk, gb);               \
+        with_bool(ktail, [&](auto kt) {                                     \
+          gemm_tn_tr_kernel<BM_, BN_, WGM_, WGN_, decltype(sk)::value,      \
+                            decltype(gat)::value, decltype(kt)::value>      \
+              <<<grid, 256, 0, s>>>(                                        \
+                  (const __bf16*)g.A, (const __bf16*)g.B, out, M0, N0,      \
+                  g.K, g.lda, g.ldb, g.ldc, g.alpha, p.kchunk, gb);         \
+        });                                                                 \
       });                                                                   \
     });                                                                     \
   else
@@ -1274,6 +1336,9 @@ int64_t ps_float_atomic_launches(int reset) {
 void ps_gemm_set_tr_tune(int bm, int bn, int target) {
   g_tr_tune = {bm, bn, target};
 }
+
+void ps_set_tr16_ktail(int on) { g_tr16_ktail.store(on ? 1 : 0); }
+int ps_tr16_ktail() { return g_tr16_ktail.load(); }
 
 void ps_gemm_set_skinny(int kmin, int bm, int bn, int splitk) {
   g_skinny_kmin.store(kmin > 0 ? kmin : 0);

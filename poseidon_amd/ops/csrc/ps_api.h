@@ -27,7 +27,13 @@ struct GemmArgs {
   // caller guarantees C is already zero (net-level zero_mt): atomic
   // split-K skips its per-launch memset
   bool c_prezeroed;
+  // >= 16 B of zeros on the operands' device, or null: what the tr16 K-tail
+  // reads for the dead k-rows of materialized operands (K % 64 != 0)
+  const void* zero = nullptr;
 };
+
+// the tr16 K-tail switch's value without PS_TR16_KTAIL (ps_set_tr16_ktail)
+constexpr int PS_TR16_KTAIL_DEFAULT = 1;
 
 // fp32 K elements per staged tile of the split-precision kernel
 constexpr int PS_SPLIT3_BK = 32;
@@ -44,6 +50,11 @@ void ps_gemm_run(const GemmArgs* g, const GemmPlan* plan, float* ws,
                  hipStream_t s);
 // tests / tuning: force the tr16 tile and split-K block target (0 = planner)
 void ps_gemm_set_tr_tune(int bm, int bn, int target);
+// tr16 K-tail, process-wide (initially PS_TR16_KTAIL=0/1, else the default
+// below): ps_gemm_plan lets K % 64 != 0 contractions with K > 64 take the
+// tr16 kernel, whose last K tile then reads its dead rows from a zero page.
+void ps_set_tr16_ktail(int on);
+int ps_tr16_ktail();
 // The skinny plan (ps_gemm_plan.h): kmin > 0 switches it on with that K-slice
 // floor, 0 switches it off; bm, bn, splitk force its tile and depth for
 // tests and tuning runs (0 = planner).

@@ -54,6 +54,9 @@ struct GemmShape {
   // is the K-slice floor (PS_SKINNY_KMIN unless a tuning run sets it)
   int skinny_kmin = 0;
   SkinnyTune skinny_tune = {0, 0, 0};
+  // tr16 K-tail: a contraction with K % 64 != 0 (and K > 64) may take the
+  // tr16 kernel, which zero-fills the dead rows of its last K tile
+  bool ktail = false;
 };
 
 // Manual override of the tr16 tile and split-K block target, 0 = planner's
@@ -245,7 +248,11 @@ inline int64_t ps_tr_tall_splitk(int M0, int N0, int K, int bm, int bn) {
 // kernel), tile (bm, bn) and split-K for the interior.
 inline bool ps_tn_tr_plan(const GemmShape& g, const TrTune& tune,
                           GemmPlan* p) {
-  if (!g.tr_ok || g.K % 64) return false;
+  if (!g.tr_ok) return false;
+  // K % 64 != 0: only with the K-tail, and only past one whole tile. The
+  // plan below is the same either way: kchunk stays a multiple of 64, so
+  // the last slice alone is ragged (an unsplit plan's kchunk rounds K up).
+  if (g.K % 64 && !(g.ktail && g.K > 64)) return false;
   const int M0 = g.M & ~15, N0 = g.N & ~63;
   if (M0 == 0 || N0 == 0) return false;
   if (g.gather_b && (M0 != g.M || N0 != g.N)) return false;
@@ -283,7 +290,8 @@ inline bool ps_tn_tr_plan(const GemmShape& g, const TrTune& tune,
   }
   if (!ps_tr_tile(bm, bn)) return false;
   const int64_t tiles = ps_tr_tiles(M0, N0, bm, bn);
-  int sk = 1, kchunk = g.K;
+  const int kpad = (g.K + 63) / 64 * 64;  // K itself without a tail
+  int sk = 1, kchunk = kpad;
   if (tiles < 384 && can_split) {
     int64_t want;
     if (tune.target > 0)
@@ -319,7 +327,7 @@ inline bool ps_tn_tr_plan(const GemmShape& g, const TrTune& tune,
       sk = (g.K + kchunk - 1) / kchunk;
     }
     if (sk > 1) ws_elems = sk * slab;
-    else kchunk = g.K;
+    else kchunk = kpad;
   }
   *p = {true, sk, ws_elems, bm, bn, kchunk, M0, N0, 0, 0};
   return true;

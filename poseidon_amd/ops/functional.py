@@ -155,6 +155,25 @@ def halo_conv_launches(reset: bool = False) -> int:
     return int(_ext().halo_conv_launches(bool(reset)))
 
 
+def set_tr16_ktail(on: bool) -> None:
+    """Toggle the K-tail of the tr16 transpose-read TN GEMM (gemm.hip
+    gemm_tn_tr_kernel): bf16 weight-gradient-class GEMMs (both operands
+    K-major, f32 out) whose contraction K is no multiple of 64 -- conv wgrads
+    with K = batch * Ho * Wo on odd feature maps, gemm_at_b -- plan tr16 like
+    any other once K > 64, and the kernel stages the last, partial K tile with
+    its missing rows read from a zero page. Off, such GEMMs run the generic
+    register-transposing kernel. Shapes with K % 64 == 0 plan and run the
+    same either way; gemm_plan(...)["tr16"] tells which path a shape takes.
+    Default on (docs/performance.md item 34); the environment variable
+    PS_TR16_KTAIL=0/1 sets it at import."""
+    if ext_available():
+        _ext().set_tr16_ktail(bool(on))
+
+
+def tr16_ktail() -> bool:
+    return bool(_ext().tr16_ktail()) if ext_available() else True
+
+
 def conv_policy_epoch() -> int:
     return _conv_policy_epoch
 
