@@ -210,6 +210,15 @@ const void* zero_page(const Tensor& like) {
 bool tr16_ktail() { return ps_tr16_ktail() != 0; }
 void set_tr16_ktail(bool on) { ps_set_tr16_ktail(on ? 1 : 0); }
 
+// NN tr16 (ps_api.h, gemm.hip gemm_nn_tr_kernel): the switch and the launch
+// counter live with the kernel, initially PS_TR16_NN, default off; planning
+// reads it. Measurements: docs/performance.md item 35.
+bool tr16_nn() { return ps_tr16_nn() != 0; }
+void set_tr16_nn(bool on) { ps_set_tr16_nn(on ? 1 : 0); }
+int64_t tr16_nn_launches(bool reset) {
+  return ps_tr16_nn_launches(reset ? 1 : 0);
+}
+
 // Skinny split-K plans (ps_gemm_plan.h): fc forward and data-gradient GEMMs
 // at batch-sized M choose tile and split depth together so that the grid
 // fills the chip. Default ON: see docs/performance.md item 31.
@@ -249,7 +258,10 @@ void run_gemm(const Tensor& A, const Tensor& B, Tensor& C,
   g.relu = relu;
   g.c_prezeroed = c_prezeroed;
   // the tr16 K-tail's zero page (a gathered B carries its own)
-  g.zero = g.in_bf16 && K % 64 && tr16_ktail() ? zero_page(A) : nullptr;
+  // and the NN tr16 K-tail's, whose switch is its own
+  const bool nn_tail = tr16_nn() && a_klast && !b_klast;
+  g.zero = g.in_bf16 && K % 64 && (tr16_ktail() || nn_tail) ? zero_page(A)
+                                                            : nullptr;
   GemmPlan plan;
   ps_gemm_plan(&g, &plan);
   TORCH_CHECK(!deterministic() || plan.splitk == 1 || plan.ws_elems > 0,
@@ -303,6 +315,7 @@ py::dict gemm_plan(int M, int N, int K, bool a_klast, bool b_klast,
   d["skinny"] = p.skinny;
   d["tr16"] = p.tr16;
   d["split3"] = p.split3;
+  d["tr16_nn"] = p.tr16_nn;
   d["splitk"] = p.splitk;
   d["ws_elems"] = p.ws_elems;
   d["bm"] = p.bm;
@@ -1949,6 +1962,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("set_tr16_tune", &ps_gemm_set_tr_tune);
   m.def("set_tr16_ktail", &set_tr16_ktail);
   m.def("tr16_ktail", &tr16_ktail);
+  m.def("set_tr16_nn", &set_tr16_nn);
+  m.def("tr16_nn", &tr16_nn);
+  m.def("tr16_nn_launches", &tr16_nn_launches);
   m.def("set_implicit_threshold", &set_implicit_threshold);
   m.def("set_packed_conv", &set_packed_conv);
   m.def("khwc_layout", &khwc_layout);

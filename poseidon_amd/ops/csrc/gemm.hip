@@ -12,7 +12,7 @@
 //
 // Every launch decision -- path, tile, split-K, K slice, XCD placement -- is
 // made once by ps_gemm_plan (policy in ps_gemm_plan.h, checked on the host by
-// tests/gemm_plan_host.cpp); ps_gemm_run executes that plan. Two kernels:
+// tests/gemm_plan_host.cpp); ps_gemm_run executes that plan. Three kernels:
 //
 // gemm_kernel, the generic tiles (PS_GEMM_TILE_LIST): every forward, every
 //   dgrad, every fp32 GEMM and whatever tr16 does not take. 256 threads = 4
@@ -35,6 +35,12 @@
 //   both operands K-major -- the weight gradients. Natural [k][col] images
 //   staged by glds and read through ds_read_b64_tr_b16. Covers the 16 x 64
 //   aligned interior; edge strips run as unsplit generic sub-problems.
+//
+// gemm_nn_tr_kernel, the NN tr16 tiles (PS_NN_TILE_LIST), opt-in
+//   (ps_set_tr16_nn): bf16 in, bf16 or f32 out, A K-last x B K-major -- the
+//   InnerProduct data gradients. A staged by glds into the generic glds
+//   image, B into the tr16 image and transpose-read; ragged M in one launch,
+//   zero-page K-tail, workspace split-K with the ordered reduce.
 //
 // Replaces the reference's cuBLAS call sites (math_functions.cu:16-65,
 // conv_layer.cu:25-121, inner_product_layer.cu:18-63).
@@ -994,6 +1000,156 @@ __global__ void splitk_reduce_tr_k(const float* __restrict__ ws,
 }
 
 // ---------------------------------------------------------------------------
+// NN tr16: A K-last ([M][lda]), B K-major ([K][ldb]) -- the InnerProduct data
+// gradients dx[M,Kin] = dy[M,Nout] @ W[Nout,Kin] -- with neither operand
+// passing through registers on its way to LDS. The generic kernel serves
+// this layout from its register-staged loop (B block-transposed in VGPRs, 24
+// ns per k-row of a 128x128 block against 14 for K-last x K-last,
+// profiles/fc_skinny_gemm.md). Here each operand keeps the image its layout
+// gives for free:
+//   A  [BM][64], the generic glds image: 16 B per lane by global_load_lds,
+//      slots swizzled at the source (GldsMap::kc / glds_col), one
+//      ds_read_b128 per fragment. A row at or past M is never addressed: the
+//      source row is clamped to M - 1, and the accumulator rows that come of
+//      it are dropped by the epilogue's row guard. So any M >= 1 runs in one
+//      launch, with no edge strip.
+//   B  [64][BN], the tr16 natural image (stage_panel_tr, 64-column
+//      sub-images, tr_swz), read through ds_read_b64_tr_b16; the reads of a
+//      k-step are batched behind one tr_wait together with A's. A bn = 128
+//      tile over N % 128 == 64 stages only its live sub-image and its dead
+//      waves skip reads, MFMAs and stores (ps_tr_sub_live / ps_tr_wave_live).
+// KT (K % 64 != 0, K % 8 == 0): the last tile of the launch's last K slice
+// zero-fills BOTH images from the zero page -- B by dead k-rows (the TAIL
+// staging), A by dead 16 B chunks (first k at or past k_end) -- because stale
+// LDS may hold NaN and 0 * NaN is NaN. kchunk is a multiple of 64, so every
+// other tile is a full one and K % 64 == 0 runs the KT = false code.
+// SPLITK: slice bz stores its raw f32 partial into slab bz of ws
+// [splitk][M][N] (gemm_epilogue), and splitk_reduce_k combines the slabs in
+// slice order: no float atomics, legal in deterministic mode.
+// Placement: ps_remap_nn -- grid.x is the ROW tile, so that the row tiles of
+// one column tile, which stage the same B panel (all of the weight traffic of
+// an fc dx), take consecutive slots on one XCD and share it through that L2.
+// LDS: 2 x (BM + BN) x 128 B = 64 KB at 128x128 (two blocks per CU, what the
+// skinny plan's slots assume), 32 KB at 64x64.
+// ---------------------------------------------------------------------------
+
+// A's [ROWS][64] glds image for the tile at k0. TAIL: the slice ends inside
+// this tile at k_end (k_end % 8 == 0): chunks at or past it load the zero page.
+template <int ROWS, bool TAIL>
+__device__ inline void stage_klast_nn(__bf16* lds, const __bf16* __restrict__ A,
+                                      int64_t lda, int m0, int M, int k0,
+                                      int k_end, const void* zero, int wid,
+                                      int lane) {
+  using MP = GldsMap<__bf16, ROWS>;
+  const int r_in = MP::r_in(lane), kc = MP::kc(lane);
+  const bool dead = TAIL && k0 + kc >= k_end;
+#pragma unroll
+  for (int i = 0; i < MP::CPL; ++i) {
+    const int ci = wid + 4 * i;
+    if (!MP::live(ci)) break;
+    const int row = min(m0 + ci * MP::RPC + r_in, M - 1);
+    const __bf16* g = A + (int64_t)row * lda + k0 + kc;
+    MP::load(lds, ci, dead ? zero : (const void*)g);
+  }
+}
+
+template <typename OUT, int BM, int BN, int WGM, int WGN, bool SPLITK, bool KT>
+__global__ __launch_bounds__(256)
+void gemm_nn_tr_kernel(const __bf16* __restrict__ A,
+                       const __bf16* __restrict__ B, OUT* __restrict__ C,
+                       float* __restrict__ ws, int M, int N, int K,
+                       int64_t lda, int64_t ldb, int64_t ldc, float alpha,
+                       int kchunk, const void* zero) {
+  constexpr int FM = BM / WGM / 16, FN = BN / WGN / 16;
+  static_assert(WGM * WGN == 4, "4 waves");
+  static_assert(BM % 32 == 0 && BN % 64 == 0, "whole glds chunks per wave");
+  __shared__ __attribute__((aligned(16))) __bf16 a_lds[2][BM * 64];
+  __shared__ __attribute__((aligned(16))) __bf16 b_lds[2][64 * BN];
+  const GemmBlock blk = ps_remap_nn(gridDim.x, gridDim.y, gridDim.z,
+                                    blockIdx.x, blockIdx.y, blockIdx.z);
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int wm = (wid / WGN) * (BM / WGM);
+  const int wn = (wid % WGN) * (BN / WGN);
+  const int m0 = blk.by * BM;
+  const int n0 = blk.bx * BN;
+  const bool live = BN > 64 ? ps_tr_wave_live(n0, wn, N) : true;
+  int k_begin = 0, k_end = K;
+  if (SPLITK) {
+    k_begin = blk.bz * kchunk;
+    k_end = min(K, k_begin + kchunk);
+    if (k_begin >= k_end) return;  // the plan leaves no slice empty
+  }
+  const int l = lane & 15, q = lane >> 4;
+
+  f32x4 acc[FM][FN] = {};
+  // the tile at k0: whole, or (KT) the one the slice ends in
+  auto stage = [&](__bf16* a_dst, __bf16* b_dst, int k0) {
+    if (KT && k0 + 64 > k_end) {
+      stage_klast_nn<BM, true>(a_dst, A, lda, m0, M, k0, k_end, zero, wid,
+                               lane);
+      stage_panel_tr<BN, false, false, true>(b_dst, B, ldb, k0, n0, N, wid,
+                                             lane, nullptr, k_end - k0, zero);
+    } else {
+      stage_klast_nn<BM, false>(a_dst, A, lda, m0, M, k0, k_end, zero, wid,
+                                lane);
+      stage_panel_tr<BN>(b_dst, B, ldb, k0, n0, N, wid, lane);
+    }
+  };
+  stage(a_lds[0], b_lds[0], k_begin);
+  __syncthreads();  // drains the in-flight glds (vmcnt 0) + barrier
+  unsigned bb[2];
+#pragma unroll
+  for (int i = 0; i < 2; ++i)
+    bb[i] = (unsigned)(unsigned long long)(
+        __attribute__((address_space(3))) __bf16*)b_lds[i];
+  int cur = 0;
+  for (int k0 = k_begin; k0 < k_end; k0 += 64) {
+    if (k0 + 64 < k_end) stage(a_lds[cur ^ 1], b_lds[cur ^ 1], k0 + 64);
+    // DEEP as in gemm_tn_tr_kernel: the 32x32 wave tile issues both 32-k
+    // halves' reads before one wait
+    constexpr int DEEP = (FM + FN <= 4) ? 2 : 1;
+    if (live) {
+      const __bf16* al = a_lds[cur];
+#pragma unroll
+      for (int kk = 0; kk < 64; kk += 32 * DEEP) {
+        bf16x8 af[DEEP][FM], bfr[DEEP][FN];
+#pragma unroll
+        for (int d = 0; d < DEEP; ++d) {
+#pragma unroll
+          for (int f = 0; f < FM; ++f) {
+            const int row = wm + f * 16 + l;
+            af[d][f] = *reinterpret_cast<const bf16x8*>(
+                &al[row * 64 + glds_col<__bf16>(row, kk + d * 32 + q * 8)]);
+          }
+#pragma unroll
+          for (int f = 0; f < FN; ++f)
+            bfr[d][f] = tr_panel_frag<BN>(bb[cur], kk + d * 32 + q * 8,
+                                          wn + f * 16, l);
+        }
+        tr_wait(af[0], bfr[0]);
+        if (DEEP == 2) tr_wait(af[DEEP - 1], bfr[DEEP - 1]);
+#pragma unroll
+        for (int d = 0; d < DEEP; ++d)
+#pragma unroll
+          for (int fm = 0; fm < FM; ++fm)
+#pragma unroll
+            for (int fn = 0; fn < FN; ++fn)
+              acc[fm][fn] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+                  af[d][fm], bfr[d][fn], acc[fm][fn], 0, 0, 0);
+      }
+    }
+    __syncthreads();
+    cur ^= 1;
+  }
+  if (!live) return;  // past the last barrier
+  gemm_epilogue<OUT, FM, FN, false, SPLITK>(acc, C, nullptr, ws, M, N, ldc,
+                                            alpha, 0.0f, false, blk.bz, m0,
+                                            n0, wm, wn, lane);
+}
+
+// ---------------------------------------------------------------------------
 // planning (ps_gemm_plan) and launching as planned (ps_gemm_run)
 // ---------------------------------------------------------------------------
 
@@ -1020,6 +1176,24 @@ static bool tn_tr_operands_ok(const GemmArgs& g) {
   }
   return true;
 }
+
+// Operand eligibility for the NN tr16 path (the shape's share is in
+// ps_nn_tr_plan): C may be bf16 or f32 with any row stride.
+static bool nn_tr_operands_ok(const GemmArgs& g) {
+  if (!g.in_bf16 || !g.a_klast || g.b_klast) return false;
+  if (g.gather_a || g.gather_b) return false;
+  if (g.bias || g.relu || g.beta != 0.0f) return false;
+  if (g.lda % 8 || g.ldb % 8) return false;
+  return (((uintptr_t)g.A | (uintptr_t)g.B) & 15) == 0;
+}
+
+// NN tr16 switch (ps_set_tr16_nn), PS_TR16_NN=0/1 at load, default off, and
+// the count of its kernel's launches.
+static std::atomic<int> g_tr16_nn{[] {
+  const char* e = getenv("PS_TR16_NN");
+  return e && *e && atoi(e) != 0 ? 1 : 0;
+}()};
+static std::atomic<int64_t> g_tr16_nn_launches{0};
 
 // The skinny plan's switch and K-slice floor (0: off), PS_SKINNY_SPLITK=0/1
 // at load; the tune is for tests / tuning only and all zero in training.
@@ -1050,6 +1224,7 @@ static GemmShape gemm_shape(const GemmArgs& g) {
   sh.only128 = !g.a_klast && g.b_klast;
   sh.deterministic = ps_deterministic() != 0;
   sh.ktail = g_tr16_ktail.load() != 0;
+  sh.nn_ok = g_tr16_nn.load() != 0 && nn_tr_operands_ok(g);
   // the fc forward / data-gradient class: a K-last A. Gathered or not: a
   // conv forward plans the same whether its column matrix exists or not
   // (the two paths give the same bits, tests/test_gpu_gather_gemm.py)
@@ -1306,9 +1481,51 @@ static void run_gemm_tn_tr(const GemmArgs& g, const GemmPlan& p, float* ws,
   }
 }
 
+// NN tr16 as planned by ps_nn_tr_plan: one GEMM launch over the whole ragged
+// M, then the shared ordered reduce when the plan split K.
+template <typename OUT>
+static void run_gemm_nn_tr(const GemmArgs& g, const GemmPlan& p, float* ws,
+                           hipStream_t s) {
+  if (p.splitk > 1 && (!ws || p.ws_elems == 0)) {
+    fprintf(stderr, "nn tr16 gemm: the plan's split-K workspace is missing\n");
+    abort();
+  }
+  const bool ktail = g.K % 64 != 0;
+  if (ktail && !g.zero) {
+    fprintf(stderr, "nn tr16 gemm: K = %d needs a zero page\n", g.K);
+    abort();
+  }
+  // rows in x: ps_remap_nn
+  dim3 grid(cdiv(g.M, p.bm), cdiv(g.N, p.bn), p.splitk);
+  g_tr16_nn_launches.fetch_add(1);
+#define PS_NN_CASE(BM_, BN_, WGM_, WGN_)                                    \
+  if (p.bm == BM_ && p.bn == BN_)                                           \
+    with_bool(p.splitk > 1, [&](auto sk) {                                  \
+      with_bool(ktail, [&](auto kt) {                                       \
+        gemm_nn_tr_kernel<OUT, BM_, BN_, WGM_, WGN_, decltype(sk)::value,   \
+                          decltype(kt)::value><<<grid, 256, 0, s>>>(        \
+            (const __bf16*)g.A, (const __bf16*)g.B, (OUT*)g.C, ws, g.M,     \
+            g.N, g.K, g.lda, g.ldb, g.ldc, g.alpha, p.kchunk, g.zero);      \
+      });                                                                   \
+    });                                                                     \
+  else
+  PS_NN_TILE_LIST(PS_NN_CASE) {
+    fprintf(stderr, "nn tr16 gemm: no %dx%d tile\n", p.bm, p.bn);
+    abort();
+  }
+#undef PS_NN_CASE
+  if (p.splitk == 1) return;
+  int64_t rb = cdiv64((int64_t)g.M * g.N, 256);
+  if (rb > 2048) rb = 2048;
+  splitk_reduce_k<OUT, false><<<dim3((unsigned)rb), 256, 0, s>>>(
+      ws, (OUT*)g.C, nullptr, g.M, g.N, g.ldc, p.splitk, g.alpha, 0.0f,
+      false);
+}
+
 extern "C" {
 
-// tr16 plan first (bf16 in, fp32 out only), else the generic plan
+// tr16 plans first (TN: bf16 in, fp32 out only; then NN, when switched on),
+// else the generic plan
 // Split-precision fp32 (gemm_split.hip), when switched on: fp32 operands in
 // one of the three layouts training reaches and at least one staged tile of
 // K. Planned like any fp32 GEMM, on its own staged K tile and without the
@@ -1321,8 +1538,9 @@ void ps_gemm_plan(const GemmArgs* g, GemmPlan* plan) {
     sh.bk = PS_SPLIT3_BK;
     sh.nt = false;
   }
-  if (!ps_tn_tr_plan(sh, g_tr_tune, plan)) ps_generic_plan(sh, plan);
-  plan->split3 = split3 && !plan->tr16;
+  if (!ps_tn_tr_plan(sh, g_tr_tune, plan) && !ps_nn_tr_plan(sh, plan))
+    ps_generic_plan(sh, plan);
+  plan->split3 = split3 && !plan->tr16 && !plan->tr16_nn;
 }
 
 void ps_set_deterministic(int on) { g_deterministic.store(on ? 1 : 0); }
@@ -1340,6 +1558,12 @@ void ps_gemm_set_tr_tune(int bm, int bn, int target) {
 void ps_set_tr16_ktail(int on) { g_tr16_ktail.store(on ? 1 : 0); }
 int ps_tr16_ktail() { return g_tr16_ktail.load(); }
 
+void ps_set_tr16_nn(int on) { g_tr16_nn.store(on ? 1 : 0); }
+int ps_tr16_nn() { return g_tr16_nn.load(); }
+int64_t ps_tr16_nn_launches(int reset) {
+  return reset ? g_tr16_nn_launches.exchange(0) : g_tr16_nn_launches.load();
+}
+
 void ps_gemm_set_skinny(int kmin, int bm, int bn, int splitk) {
   g_skinny_kmin.store(kmin > 0 ? kmin : 0);
   g_skinny_tune = {bm, bn, splitk};
@@ -1350,6 +1574,9 @@ int ps_gemm_skinny_kmin() { return g_skinny_kmin.load(); }
 void ps_gemm_run(const GemmArgs* g, const GemmPlan* plan, float* ws,
                  hipStream_t s) {
   if (plan->tr16) return run_gemm_tn_tr(*g, *plan, ws, s);
+  if (plan->tr16_nn)
+    return g->out_f32 ? run_gemm_nn_tr<float>(*g, *plan, ws, s)
+                      : run_gemm_nn_tr<__bf16>(*g, *plan, ws, s);
   run_gemm_generic(*g, *plan, ws, s);
 }
 

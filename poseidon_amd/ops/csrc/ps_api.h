@@ -27,8 +27,8 @@ struct GemmArgs {
   // caller guarantees C is already zero (net-level zero_mt): atomic
   // split-K skips its per-launch memset
   bool c_prezeroed;
-  // >= 16 B of zeros on the operands' device, or null: what the tr16 K-tail
-  // reads for the dead k-rows of materialized operands (K % 64 != 0)
+  // >= 16 B of zeros on the operands' device, or null: what the tr16 K-tails
+  // (TN and NN) read for the dead k of materialized operands (K % 64 != 0)
   const void* zero = nullptr;
 };
 
@@ -55,6 +55,14 @@ void ps_gemm_set_tr_tune(int bm, int bn, int target);
 // tr16 kernel, whose last K tile then reads its dead rows from a zero page.
 void ps_set_tr16_ktail(int on);
 int ps_tr16_ktail();
+// NN tr16, process-wide (initially PS_TR16_NN=0/1, default off): ps_gemm_plan
+// sends bf16 GEMMs with a K-last A and a K-major B (the InnerProduct data
+// gradients) to gemm_nn_tr_kernel where ps_nn_tr_plan takes them. Its K-tail
+// (K % 64 != 0) needs GemmArgs::zero and does not depend on the TN switch.
+void ps_set_tr16_nn(int on);
+int ps_tr16_nn();
+// host-side count of gemm_nn_tr_kernel launches
+int64_t ps_tr16_nn_launches(int reset);
 // The skinny plan (ps_gemm_plan.h): kmin > 0 switches it on with that K-slice
 // floor, 0 switches it off; bm, bn, splitk force its tile and depth for
 // tests and tuning runs (0 = planner).

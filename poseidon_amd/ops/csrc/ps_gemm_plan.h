@@ -27,6 +27,7 @@ struct GemmPlan {
   int ry, cx;        // generic only: 2D-XCD rectangle in tiles (0: none)
   bool skinny;       // generic only: made by ps_skinny_plan (for reporting)
   bool split3;       // generic only: fp32 in, run by the bf16x3 split kernel
+  bool tr16_nn;      // bf16 NN tr16 kernel (ps_nn_tr_plan): K-last A, K-major B
 };
 
 // Manual override of the skinny plan's tile and depth, 0 = planner's choice.
@@ -57,6 +58,10 @@ struct GemmShape {
   // tr16 K-tail: a contraction with K % 64 != 0 (and K > 64) may take the
   // tr16 kernel, which zero-fills the dead rows of its last K tile
   bool ktail = false;
+  // the NN tr16 switch is on and the operands can take gemm_nn_tr_kernel:
+  // bf16, a K-last A and a K-major B, no gathers, bias, ReLU or beta, 16 B
+  // aligned rows (gemm_shape() folds all of it in, as it does for tr_ok)
+  bool nn_ok = false;
 };
 
 // Manual override of the tr16 tile and split-K block target, 0 = planner's
@@ -166,19 +171,25 @@ inline const GemmTile* ps_gemm_tile(int bm, int bn) {
   return nullptr;
 }
 
+// the cost model above for one tile (per unit of K)
+inline double ps_gemm_tile_cost(int M, int N, int bm, int bn) {
+  const double ALPHA = 400.0;
+  int64_t tm = (M + bm - 1) / bm, tn = (N + bn - 1) / bn;
+  double flops = (double)(tm * bm) * (tn * bn) / ALPHA;  // (x K, common)
+  double staging = (double)tm * bm * tn + (double)tn * bn * tm;
+  return flops + staging;
+}
+
 inline void pick_gemm_tile(int M, int N, int* bm_out, int* bn_out,
                            bool narrow) {
   int n;
   const GemmTile* tiles = ps_gemm_tiles(&n);
-  const double ALPHA = 400.0;
   double best = -1.0;
   int64_t best_npad = 0;
   for (int i = 0; i < n; ++i) {
     const int bm = tiles[i].bm, bn = tiles[i].bn;
-    int64_t tm = (M + bm - 1) / bm, tn = (N + bn - 1) / bn;
-    double flops = (double)(tm * bm) * (tn * bn) / ALPHA;  // (x K, common)
-    double staging = (double)tm * bm * tn + (double)tn * bn * tm;
-    double cost = flops + staging;
+    int64_t tn = (N + bn - 1) / bn;
+    double cost = ps_gemm_tile_cost(M, N, bm, bn);
     if (tiles[i].narrow_only && (!narrow || tn * bn >= best_npad)) continue;
     if (best < 0 || cost < best) {
       best = cost;
@@ -494,6 +505,70 @@ inline void ps_generic_plan(const GemmShape& g, GemmPlan* p,
 }
 
 // ---------------------------------------------------------------------------
+// NN tr16 plan (gemm.hip gemm_nn_tr_kernel): bf16 GEMMs with a K-last A and a
+// K-major B -- the InnerProduct data gradients dx = dy @ W, and whatever else
+// has that layout -- once the switch is on (GemmShape::nn_ok). Both operands
+// go straight to LDS; C is bf16 or f32; M is ragged (the kernel clamps A's
+// rows), N is a multiple of 64 (a bn = 128 grid runs its last column tile
+// ragged, ps_tr_wave_live), K a multiple of 8 (the K-tail zero-fills whole
+// 16 B chunks of A) and at least one staged tile.
+// X(bm, bn, wave rows, wave cols): the ONE list the launcher (gemm.hip
+// PS_NN_CASE) and the planner draw from. No 32- or 16-row tile: at M = 32
+// the 64x64 tile, half of it padding, beat the generic 32x128 plans on all
+// three VGG-16 fc dx shapes (profiles/tr16_nn_gemm.md).
+// ---------------------------------------------------------------------------
+#define PS_NN_TILE_LIST(X) X(128, 128, 2, 2) X(64, 64, 2, 2)
+
+inline const TrTile* ps_nn_tile(int bm, int bn) {
+#define PS_NN_ROW(BM_, BN_, WGM_, WGN_) {BM_, BN_, WGM_, WGN_},
+  static const TrTile tiles[] = {PS_NN_TILE_LIST(PS_NN_ROW)};
+#undef PS_NN_ROW
+  for (const TrTile& t : tiles)
+    if (t.bm == bm && t.bn == bn) return &t;
+  return nullptr;
+}
+
+// double-buffered [bm][BK] + [BK][bn] bf16 images: 64 KB at 128x128, two
+// blocks per CU, the occupancy PS_SKINNY_SLOTS assumes
+inline int ps_nn_lds_bytes(int bm, int bn) { return ps_tr_lds_bytes(bm, bn); }
+
+// Tile: pick_gemm_tile's cost model over the NN tiles. Depth: where the
+// skinny conditions hold (a batch-sized M on a thin grid, the skinny switch
+// on) the skinny plan's, on 64-row staged tiles, with its 64x64 fallback and
+// its test / tuning override; unsplit otherwise. A split always goes through
+// the f32 workspace [splitk][M][N] and the ordered reduce -- never atomics --
+// so an atomic-capable C and deterministic mode plan like any other.
+// ps_skinny_depth keeps the workspace under PS_WS_CAP_BYTES by shrinking the
+// depth and leaves no slice empty; kchunk is a multiple of 64, so only the
+// last slice of a K % 64 != 0 contraction ends in a partial tile.
+inline bool ps_nn_tr_plan(const GemmShape& g, GemmPlan* p) {
+  if (!g.nn_ok) return false;
+  if (g.M < 1 || g.N % 64 || g.K % 8 || g.K < PS_TR_BK) return false;
+  int bm = 0, bn = 0;
+  double best = -1.0;
+#define PS_NN_PICK(BM_, BN_, WGM_, WGN_)                          \
+  if (const double c = ps_gemm_tile_cost(g.M, g.N, BM_, BN_);     \
+      best < 0 || c < best)                                       \
+    best = c, bm = BM_, bn = BN_;
+  PS_NN_TILE_LIST(PS_NN_PICK)
+#undef PS_NN_PICK
+  *p = {false, 1, 0, bm, bn, 0, 0, 0, 0, 0};
+  p->tr16_nn = true;
+  const int64_t tiles =
+      (int64_t)((g.M + bm - 1) / bm) * ((g.N + bn - 1) / bn);
+  if (tiles < 384 && g.skinny_kmin > 0 && g.M <= PS_SKINNY_MAX_M) {
+    GemmShape s = g;
+    s.bk = PS_TR_BK;
+    if (!ps_nn_tile(s.skinny_tune.bm, s.skinny_tune.bn))
+      s.skinny_tune.bm = s.skinny_tune.bn = 0;
+    ps_skinny_plan(s, p);  // the 64x64 it may fall back to is an NN tile
+  }
+  const int slice = (g.K + p->splitk - 1) / p->splitk;
+  p->kchunk = (slice + PS_TR_BK - 1) / PS_TR_BK * PS_TR_BK;
+  return true;
+}
+
+// ---------------------------------------------------------------------------
 // Block-index remaps. The hardware dispatcher places linear block l on XCD
 // l % 8, each with a private 4 MiB L2. Every remap is a PERMUTATION of its
 // launch grid (tests/gemm_plan_host.cpp enumerates them); the kernels call
@@ -520,6 +595,23 @@ PS_HD inline GemmBlock ps_remap_linear(int nbx, int nby, int nbz, int bx,
     bz = (int)(id / ((int64_t)nbx * nby));
   }
   return {bx, by, bz};
+}
+
+// NN tr16 placement. The launch grid is (row tiles, column tiles, slices) --
+// rows in x, the fastest dimension -- and goes through the linear swizzle as
+// it stands, so the flattened index runs over the row tiles of ONE column
+// tile and slice before it moves to the next column tile. Those row tiles
+// (two at M = 256) stage the same [kchunk][bn] panel of B, which in an fc
+// data gradient is all of the weight traffic (A = dy is M x K, a few MB
+// shared by everyone): they get consecutive slots on one XCD, so the second
+// one's B reads hit that XCD's L2 while the first one's are in flight or just
+// landed. Grids that are no multiple of 8 blocks keep the identity, where the
+// same row tiles are consecutive in dispatch order on neighbouring XCDs.
+// Returns {bx = column tile, by = row tile, bz}.
+PS_HD inline GemmBlock ps_remap_nn(int nby, int nbx, int nbz, int x, int y,
+                                   int z) {
+  const GemmBlock b = ps_remap_linear(nby, nbx, nbz, x, y, z);
+  return {b.by, b.bx, b.bz};
 }
 
 // The planned rectangle (ps_pick_xcd_rect): XCD k owns rectangle k, and its

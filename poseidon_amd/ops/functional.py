@@ -174,6 +174,33 @@ def tr16_ktail() -> bool:
     return bool(_ext().tr16_ktail()) if ext_available() else True
 
 
+def set_tr16_nn(on: bool) -> None:
+    """Toggle the NN tr16 GEMM (gemm.hip gemm_nn_tr_kernel): bf16 GEMMs with
+    a K-last A and a K-major B -- linear_backward's dx = dy @ W, bf16 or f32
+    out -- stage both operands straight into LDS (A by global_load_lds into
+    the generic swizzled image, B into the tr16 image read through
+    ds_read_b64_tr_b16) instead of block-transposing B through registers.
+    Taken when N % 64 == 0, K % 8 == 0, K >= 64, rows 16 B aligned, no bias,
+    ReLU or beta; any M >= 1. A split goes through the f32 workspace and the
+    ordered reduce, never atomics, so deterministic mode may use it;
+    gemm_plan(...)["tr16_nn"] tells which path a shape takes. Default off
+    (docs/performance.md item 35); the environment variable PS_TR16_NN=0/1
+    sets it at import."""
+    if ext_available():
+        _ext().set_tr16_nn(bool(on))
+
+
+def tr16_nn() -> bool:
+    return bool(_ext().tr16_nn()) if ext_available() else False
+
+
+def tr16_nn_launches(reset: bool = False) -> int:
+    """Launches so far of the NN tr16 GEMM kernel (a host-side counter)."""
+    if not ext_available():
+        return 0
+    return int(_ext().tr16_nn_launches(bool(reset)))
+
+
 def conv_policy_epoch() -> int:
     return _conv_policy_epoch
 
@@ -275,7 +302,7 @@ def fused_weight_tail() -> bool:
 def gemm_plan(M: int, N: int, K: int, a_klast: bool, b_klast: bool,
               bf16: bool, out_f32: bool = True, bias: bool = False) -> dict:
     """The launch plan of the test GEMM entry for this shape right now:
-    tr16, split3, splitk, ws_elems, bm, bn, kchunk, grid_z, skinny.
+    tr16, tr16_nn, split3, splitk, ws_elems, bm, bn, kchunk, grid_z, skinny.
     out_f32=False (a C of the input type) and bias=True plan what
     linear_forward and linear_backward's dx run."""
     return dict(_ext().gemm_plan(int(M), int(N), int(K), bool(a_klast),

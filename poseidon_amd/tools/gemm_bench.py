@@ -2,11 +2,17 @@
 rules 24/25). Usage:
 
     python -m poseidon_amd.tools.gemm_bench [--size 4096] [--dtype bf16]
-        [--layout nt|nn|tn] [--reps 20] [--split]
+        [--layout nt|nn|tn] [--reps 20] [--split] [--nn-ab]
 
 --split (fp32 only) times the exact fp32 path and then the split-precision
 path (ops.set_fp32_split) in the same process after one clock ramp, and
 prints both with their ratio; TF/s is effective, from the fp32 FLOP count.
+
+Every run prints the path its plan takes (generic, tr16, tr16_nn, split3).
+--layout nn picks up the NN tr16 switch from PS_TR16_NN; --nn-ab (bf16, nn)
+times the switch off and then on in the same process after one clock ramp
+each. The test entry's C is f32: for the bf16-out plans of linear_backward's
+dx, time ops.linear_backward itself.
 """
 
 import argparse
@@ -24,9 +30,13 @@ def main(argv=None):
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--split", action="store_true",
                     help="also time the bf16x3 split path (needs --dtype fp32)")
+    ap.add_argument("--nn-ab", action="store_true",
+                    help="time the NN tr16 switch off, then on (bf16, nn)")
     args = ap.parse_args(argv)
     if args.split and args.dtype != "fp32":
         ap.error("--split is valid with --dtype fp32 only")
+    if args.nn_ab and (args.dtype, args.layout) != ("bf16", "nn"):
+        ap.error("--nn-ab is valid with --dtype bf16 --layout nn only")
 
     from poseidon_amd.ops._backend import load
     ext = load()
@@ -43,6 +53,14 @@ def main(argv=None):
     opB = torch.randn(K, N, generator=g)
     A = (opA if ak else opA.t()).contiguous().to("cuda", dt)
     B = (opB.t() if bk else opB).contiguous().to("cuda", dt)
+
+    def path():
+        plan = ext.gemm_plan(M, N, K, ak, bk, args.dtype == "bf16", True,
+                             False)
+        name = next((k for k in ("tr16", "tr16_nn", "split3") if plan[k]),
+                    "generic")
+        return (f"{name} {plan['bm']}x{plan['bn']} splitk {plan['splitk']} "
+                f"kchunk {plan['kchunk']}")
 
     def measure(split):
         # correctness spot-check FIRST: the CPU reference matmul takes
@@ -67,17 +85,23 @@ def main(argv=None):
         tf = 2.0 * M * N * K / dt_s / 1e12
         name = args.dtype + (" split" if split else "")
         print(f"{args.layout} {name} {M}x{N}x{K}: {tf:.1f} TF/s "
-              f"({dt_s * 1e3:.3f} ms), max_err={err:.3g}")
+              f"({dt_s * 1e3:.3f} ms), max_err={err:.3g} [{path()}]")
         return dt_s
 
     ref = (opA.to(dt).float() @ opB.to(dt).float())
-    was = ext.fp32_split()
+    was, was_nn = ext.fp32_split(), ext.tr16_nn()
     try:
+        if args.nn_ab:
+            ext.set_tr16_nn(False)
         exact = measure(False)
         if args.split:
             print(f"split / exact speed: {exact / measure(True):.2f}x")
+        if args.nn_ab:
+            ext.set_tr16_nn(True)
+            print(f"tr16_nn / generic speed: {exact / measure(False):.2f}x")
     finally:
         ext.set_fp32_split(was)
+        ext.set_tr16_nn(was_nn)
 
 
 if __name__ == "__main__":
