@@ -307,42 +307,32 @@ class MVNLayer(Layer):
         mp = self.param.mvn_param
         self.norm_var = bool(mp.normalize_variance) if mp is not None else True
         self.across = bool(mp.across_channels) if mp is not None else False
-        self.eps = 1e-10
+        self.eps = ops.MVN_EPS
+        self._stats = None  # fused kernels: fp32 (mean, rstd) per set
+        self._std = None    # composite: std in the compute type
 
     def reshape(self, bottom, top) -> None:
         top[0].reshape(bottom[0].shape)
 
-    def _dims(self, x):
-        return (1, 2, 3) if self.across else (2, 3)
-
     def forward(self, bottom, top) -> None:
         x = bottom[0].data
-        dims = self._dims(x)
-        mean = x.mean(dim=dims, keepdim=True)
-        if self.norm_var:
-            var = (x * x).mean(dim=dims, keepdim=True) - mean * mean
-            std = (var + self.eps).sqrt()
-            self._std = std
-            top[0].data = (x - mean) / std
-        else:
-            top[0].data = x - mean
+        fused = ops.mvn_fused() and ops.mvn_fused_ok(x)
+        y, saved = ops.mvn_forward(x, self.across, self.norm_var)
+        # the fused backward recomputes y from x and the statistics; the
+        # composite one reads top.data and std
+        self._stats, self._std = (saved, None) if fused else (None, saved)
+        top[0].data = y
 
     def backward(self, top, propagate_down, bottom) -> None:
         if not propagate_down[0]:
             return
         x, dy = bottom[0].data, top[0].diff
-        dims = self._dims(x)
-        m = 1.0
-        for d in dims:
-            m *= x.shape[d]
-        if self.norm_var:
-            y = top[0].data
-            # Caffe mvn_layer.cpp backward: dx = (dy - mean(dy) - y*mean(dy*y))/std
-            mean_dy = dy.mean(dim=dims, keepdim=True)
-            mean_dyy = (dy * y).mean(dim=dims, keepdim=True)
-            bottom[0].diff = (dy - mean_dy - y * mean_dyy) / self._std
+        if self._stats is not None:
+            bottom[0].diff = ops.mvn_backward(x, dy, self._stats, self.across,
+                                              self.norm_var)
         else:
-            bottom[0].diff = dy - dy.mean(dim=dims, keepdim=True)
+            bottom[0].diff = ops.mvn_backward(x, dy, self._std, self.across,
+                                              self.norm_var, y=top[0].data)
 
 
 @register_layer("SILENCE")

@@ -1171,6 +1171,68 @@ int64_t lrn_within_launches(bool reset) {
   return ps_lrn_within_launches(reset ? 1 : 0);
 }
 
+// MVN (mvn.hip): (N, C, H, W) channels-last, or (N, K) read as (N, K, 1, 1).
+struct MvnArgs {
+  Tensor x;  // layout-normalised
+  int64_t N, C, P;
+};
+MvnArgs mvn_args(const Tensor& x) {
+  check_float_like(x, "x");
+  TORCH_CHECK(x.dim() == 2 || x.dim() == 4, "mvn: needs a 2D or 4D tensor");
+  const bool d4 = x.dim() == 4;
+  return {d4 ? cl4(x) : x.contiguous(), x.size(0), x.size(1),
+          d4 ? x.size(2) * x.size(3) : 1};
+}
+Tensor mvn_like(const Tensor& x) {
+  return x.dim() == 4 ? empty_cl(x.sizes(), x.options())
+                      : at::empty(x.sizes(), x.options());
+}
+bool mvn_vec(const Tensor& a, const Tensor& b, const Tensor& c) {
+  return (((uintptr_t)a.data_ptr() | (uintptr_t)b.data_ptr() |
+           (uintptr_t)c.data_ptr()) & 15) == 0;
+}
+Tensor mvn_ws(const MvnArgs& a, bool across, bool backward, bool vec) {
+  return at::empty({ps_mvn_ws_floats(a.N, a.C, a.P, (int)a.x.element_size(),
+                                     across, backward, vec)},
+                   a.x.options().dtype(at::kFloat));
+}
+
+std::tuple<Tensor, Tensor> mvn_forward(const Tensor& x, bool across,
+                                       bool norm_var) {
+  const MvnArgs a = mvn_args(x);
+  Tensor y = mvn_like(x);
+  Tensor stats = at::empty({across ? a.N : a.N * a.C, 2},
+                           x.options().dtype(at::kFloat));
+  const bool vec = mvn_vec(a.x, a.x, y);
+  Tensor ws = mvn_ws(a, across, false, vec);
+  PS_CALL(mvn_fwd, is_bf16(x), P(a.x), P(y), stats.data_ptr<float>(),
+          ws.numel() ? ws.data_ptr<float>() : nullptr, a.N, a.C, a.P, across,
+          norm_var, vec, stream());
+  return {y, stats};
+}
+
+Tensor mvn_backward(const Tensor& x, const Tensor& dy, const Tensor& stats,
+                    bool across, bool norm_var) {
+  const MvnArgs a = mvn_args(x);
+  TORCH_CHECK(dy.sizes() == x.sizes() && dy.is_cuda() &&
+              dy.scalar_type() == x.scalar_type(), "mvn: dy must match x");
+  TORCH_CHECK(stats.is_cuda() && stats.scalar_type() == at::kFloat &&
+              stats.is_contiguous() && stats.dim() == 2 &&
+              stats.size(0) == (across ? a.N : a.N * a.C) &&
+              stats.size(1) == 2,
+              "mvn: stats must be the forward's fp32 [sets, 2] tensor");
+  Tensor dy_n = x.dim() == 4 ? cl4(dy) : dy.contiguous();
+  Tensor dx = mvn_like(x);
+  const bool vec = mvn_vec(a.x, dy_n, dx);
+  Tensor ws = mvn_ws(a, across, true, vec);
+  PS_CALL(mvn_bwd, is_bf16(x), P(a.x), P(dy_n), P(dx),
+          stats.data_ptr<float>(), ws.numel() ? ws.data_ptr<float>() : nullptr,
+          a.N, a.C, a.P, across, norm_var, vec, stream());
+  return dx;
+}
+
+int64_t mvn_launches(bool reset) { return ps_mvn_launches(reset ? 1 : 0); }
+
 // ---------------------------------------------------------------------------
 // Fused backward tails of a conv block (conv -> relu -> [lrn] -> [max pool]):
 // one pass over the conv output writes dx, already masked by the in-place
@@ -2010,6 +2072,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("lrn_within_ok", &ps_lrn_within_ok);
   m.def("lrn_within_launches", &lrn_within_launches);
   m.def("set_lrn_within_strip", &ps_lrn_within_set_strip);
+  m.def("mvn_forward", &mvn_forward);
+  m.def("mvn_backward", &mvn_backward);
+  m.def("mvn_launches", &mvn_launches);
+  m.def("set_mvn_split", &ps_mvn_set_split);
   m.def("softmax_forward", &softmax_forward);
   m.def("softmax_backward", &softmax_backward);
   m.def("softmax_loss_forward", &softmax_loss_forward);

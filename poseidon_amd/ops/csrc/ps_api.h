@@ -217,6 +217,27 @@ void ps_lrn_within_set_strip(int n);
 // host-side count of the launches above
 int64_t ps_lrn_within_launches(int reset);
 
+// mvn.hip: mean-variance normalisation of N images of P pixels x C channels,
+// channels innermost; across: one set per image, else one per (image,
+// channel). fwd (x, y, stats, ws, N, C, P, across, norm_var, vec) writes
+// (mean, rstd) fp32 pairs, [N] or [N * C] of them; bwd (x, dy, dx, stats, ws,
+// ...) reads them. vec: x, dy and the output are 16-byte aligned. ws:
+// ps_mvn_ws_floats() floats (0: none needed). Not in place.
+int64_t ps_mvn_ws_floats(int64_t N, int64_t C, int64_t P, int itemsize,
+                         int across, int backward, int vec);
+void ps_mvn_fwd_f32(const float*, float*, float*, float*, int64_t, int64_t,
+                    int64_t, int, int, int, hipStream_t);
+void ps_mvn_fwd_bf16(const void*, void*, float*, float*, int64_t, int64_t,
+                     int64_t, int, int, int, hipStream_t);
+void ps_mvn_bwd_f32(const float*, const float*, float*, float*, float*,
+                    int64_t, int64_t, int64_t, int, int, int, hipStream_t);
+void ps_mvn_bwd_bf16(const void*, const void*, void*, float*, float*, int64_t,
+                     int64_t, int64_t, int, int, int, hipStream_t);
+// tests only: chunks per slab of the split regime (0 = the plan's own)
+void ps_mvn_set_split(int n);
+// host-side count of the launches above
+int64_t ps_mvn_launches(int reset);
+
 // softmax.hip
 void ps_softmax_rows_f32(const float*, float*, int64_t, int, hipStream_t);
 void ps_softmax_bwd_rows_f32(const float*, const float*, float*, int64_t, int,

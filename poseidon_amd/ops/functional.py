@@ -725,6 +725,84 @@ def lrn_within_backward(x, dy, size: int, alpha: float, beta: float,
 
 
 # ---------------------------------------------------------------------------
+# MVN: y = (x - mean) / sqrt(var + eps) over each (image, channel) or, with
+# across, each image; biased variance; normalize_variance off stops at
+# x - mean. GPU, fp32 or bf16, 2-D or 4-D: one kernel each way (mvn.hip; two
+# when a slab is split over blocks), fp32 statistics from centred values, and
+# the backward recomputes y from x and the saved (mean, rstd). Everything
+# else runs the composite below in the tensor's own type.
+# ---------------------------------------------------------------------------
+
+_mvn_fused = os.environ.get("PS_MVN_FUSED", "1") not in ("", "0")
+MVN_EPS = 1e-10
+
+
+def set_mvn_fused(on: bool) -> None:
+    """Toggle the fused MVN kernels (default on; the environment variable
+    PS_MVN_FUSED=0/1 sets it at import). Off puts the GPU back on the
+    composite, for A/B runs."""
+    global _mvn_fused
+    _mvn_fused = bool(on)
+
+
+def mvn_fused() -> bool:
+    return _mvn_fused
+
+
+def mvn_fused_ok(x) -> bool:
+    """Whether the fused kernels take x."""
+    return bool(x.is_cuda and x.dim() in (2, 4)
+                and x.dtype in (torch.float32, torch.bfloat16))
+
+
+def _set_mvn_split(n: int) -> None:
+    """Tests only: force the split regime with n blocks per slab (0 = the
+    plan's own choice)."""
+    if ext_available():
+        _ext().set_mvn_split(int(n))
+
+
+def mvn_launches(reset: bool = False) -> int:
+    """Launches so far of the fused MVN kernels (a host-side counter)."""
+    if not ext_available():
+        return 0
+    return int(_ext().mvn_launches(bool(reset)))
+
+
+def _mvn_dims(across: bool):
+    return (1, 2, 3) if across else (2, 3)
+
+
+def mvn_forward(x, across: bool, norm_var: bool):
+    """-> (y, saved). Fused: saved is the fp32 [sets, 2] (mean, rstd) tensor.
+    Composite: saved is std (None without norm_var), and the backward also
+    wants y."""
+    if _mvn_fused and mvn_fused_ok(x):
+        return _ext().mvn_forward(x, bool(across), bool(norm_var))
+    dims = _mvn_dims(across)
+    mean = x.mean(dim=dims, keepdim=True)
+    if norm_var:
+        var = (x * x).mean(dim=dims, keepdim=True) - mean * mean
+        std = (var + MVN_EPS).sqrt()
+        return (x - mean) / std, std
+    return x - mean, None
+
+
+def mvn_backward(x, dy, saved, across: bool, norm_var: bool, y=None):
+    """saved: what mvn_forward returned, which also names the path -- a 2-D
+    tensor is the fused kernels' statistics. y: the composite's output."""
+    if x.is_cuda and saved is not None and saved.dim() == 2:
+        return _ext().mvn_backward(x, dy, saved, bool(across), bool(norm_var))
+    dims = _mvn_dims(across)
+    if norm_var:
+        # Caffe mvn_layer.cpp backward: dx = (dy - mean(dy) - y*mean(dy*y))/std
+        mean_dy = dy.mean(dim=dims, keepdim=True)
+        mean_dyy = (dy * y).mean(dim=dims, keepdim=True)
+        return (dy - mean_dy - y * mean_dyy) / saved
+    return dy - dy.mean(dim=dims, keepdim=True)
+
+
+# ---------------------------------------------------------------------------
 # Fused backward tails of a conv block: conv -> relu -> [lrn] -> [max pool].
 # One kernel writes the conv's top diff (already masked by the in-place
 # ReLU) and adds its column sum into the conv's bias gradient. The CPU path

@@ -24,6 +24,7 @@ sources = [
         "pool.hip",
         "lrn.hip",
         "lrn_within.hip",
+        "mvn.hip",
         "softmax.hip",
         "sgd.hip",
         "im2col.hip",
