@@ -67,8 +67,30 @@ class SoftmaxLayer(Layer):
 
 @register_layer("SOFTMAX_LOSS")
 class SoftmaxWithLossLayer(LossLayer):
+    """Two label shapes (softmax_loss_layer.cpp:46-55, :76-85 with
+    spatial_dim = H*W): one label per (n, h, w) of an (N, C, H, W) bottom is
+    the dense loss -- softmax over C at every position, normalised by N*H*W,
+    the 4-D tensor handed to the op as it lies; one label per image keeps
+    the classifier reading of the bottom as (N, C*H*W)."""
+
+    def reshape(self, bottom, top) -> None:
+        super().reshape(bottom, top)
+        b, n = bottom[0], bottom[1].count
+        dense = b.num * b.height * b.width
+        self._dense = b.height * b.width > 1 and n == dense
+        if not self._dense and n != b.num:
+            raise ValueError(
+                f"SOFTMAX_LOSS {self.name!r}: bottom of shape {b.shape} takes "
+                f"{b.num} labels (one per image)"
+                + (f" or {dense} (one per position)" if dense != b.num else "")
+                + f", got a label blob of shape {bottom[1].shape}")
+
     def forward(self, bottom, top) -> None:
-        logits = bottom[0].data.reshape(bottom[0].num, -1)
+        b = bottom[0]
+        if self._dense:
+            logits = b.data.view(b.num, b.channels, b.height, b.width)
+        else:
+            logits = b.data.reshape(b.num, -1)
         labels = bottom[1].data.reshape(-1)
         loss, prob = ops.softmax_loss_forward(logits, labels)
         self._prob = prob

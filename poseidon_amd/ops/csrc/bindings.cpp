@@ -1436,6 +1436,87 @@ Tensor softmax_loss_backward(const Tensor& prob, const Tensor& labels,
   return dx;
 }
 
+// Dense (per-position) softmax loss: (N, C, H, W) logits, one label per
+// (n, h, w). The channels-last rows are the reference's label order, so the
+// tensor goes to the kernels as it lies. lane_groups: softmax_dense.hip where
+// its plan takes the shape, else (and when off) the wave-per-row kernels of
+// softmax.hip with rows = N*H*W.
+struct DenseLossArgs {
+  Tensor t;       // channels-last, 16-byte aligned
+  Tensor labels;  // fp32, contiguous
+  int64_t rows;
+  int C;
+  bool lane_groups;
+};
+DenseLossArgs dense_loss_args(const Tensor& t, const Tensor& labels,
+                              bool lane_groups, const char* name) {
+  check_float_like(t, name);
+  TORCH_CHECK(t.dim() == 4, "softmax loss (dense): ", name, " must be 4-D");
+  const int64_t rows = t.size(0) * t.size(2) * t.size(3);
+  TORCH_CHECK(labels.is_cuda() && labels.numel() == rows,
+              "softmax loss (dense): ", name, " of shape ", t.sizes(),
+              " needs N*H*W = ", rows, " labels on its device, got shape ",
+              labels.sizes());
+  TORCH_CHECK(rows >= 1 && t.size(1) >= 1 && t.size(1) < (1 << 30),
+              "softmax loss (dense): empty or oversized ", name);
+  Tensor tc = cl4(t);
+  if ((uintptr_t)tc.data_ptr() & 15)  // an offset view: the vector loads
+    tc = tc.clone(at::MemoryFormat::ChannelsLast);  // want 16 bytes
+  return {tc, labels.contiguous().to(at::kFloat), rows, (int)t.size(1),
+          lane_groups &&
+              ps_softmax_dense_ok(rows, t.size(1), (int)t.element_size()) != 0};
+}
+
+// max_blocks: cap of the lane-group forward's grid (0 = the plan's own)
+std::vector<Tensor> softmax_loss_dense_forward(const Tensor& logits,
+                                               const Tensor& labels,
+                                               bool lane_groups,
+                                               int64_t max_blocks) {
+  TORCH_CHECK(max_blocks >= 0 && max_blocks < (1 << 30),
+              "softmax loss (dense): bad max_blocks");
+  const DenseLossArgs a = dense_loss_args(logits, labels, lane_groups,
+                                          "logits");
+  Tensor prob = empty_cl(a.t.sizes(), a.t.options());
+  Tensor loss = at::zeros({}, a.t.options().dtype(at::kFloat));
+  Tensor part;  // deterministic mode: per-block (per-row) terms, summed in order
+  if (deterministic())
+    part = at::empty({a.lane_groups
+                          ? ps_softmax_dense_blocks(a.rows, a.C,
+                                                    (int)a.t.element_size(),
+                                                    (int)max_blocks)
+                          : a.rows},
+                     loss.options());
+  float* pp = part.defined() ? part.data_ptr<float>() : nullptr;
+  if (a.lane_groups) {  // the blocks' terms arrive already divided by rows
+    PS_CALL(softmax_dense_fwd, is_bf16(a.t), P(a.t),
+            a.labels.data_ptr<float>(), P(prob), loss.data_ptr<float>(), pp,
+            a.rows, a.C, (int)max_blocks, stream());
+    return {loss, prob};
+  }
+  PS_CALL(softmax_loss_fwd, is_bf16(a.t), P(a.t), a.labels.data_ptr<float>(),
+          P(prob), loss.data_ptr<float>(), pp, a.rows, a.C, stream());
+  loss.div_((double)a.rows);
+  return {loss, prob};
+}
+
+Tensor softmax_loss_dense_backward(const Tensor& prob, const Tensor& labels,
+                                   double loss_weight, bool lane_groups) {
+  const DenseLossArgs a = dense_loss_args(prob, labels, lane_groups, "prob");
+  Tensor dx = empty_cl(a.t.sizes(), a.t.options());
+  const float w = (float)(loss_weight / a.rows);
+  if (a.lane_groups)
+    PS_CALL(softmax_dense_bwd, is_bf16(a.t), P(a.t),
+            a.labels.data_ptr<float>(), P(dx), a.rows, a.C, w, stream());
+  else
+    PS_CALL(softmax_loss_bwd, is_bf16(a.t), P(a.t), a.labels.data_ptr<float>(),
+            P(dx), a.rows, a.C, w, stream());
+  return dx;
+}
+
+int64_t softmax_dense_launches(bool reset) {
+  return ps_softmax_dense_launches(reset ? 1 : 0);
+}
+
 // ---------------------------------------------------------------------------
 // neuron ops
 // ---------------------------------------------------------------------------
@@ -2080,6 +2161,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("softmax_backward", &softmax_backward);
   m.def("softmax_loss_forward", &softmax_loss_forward);
   m.def("softmax_loss_backward", &softmax_loss_backward);
+  m.def("softmax_loss_dense_forward", &softmax_loss_dense_forward);
+  m.def("softmax_loss_dense_backward", &softmax_loss_dense_backward);
+  m.def("softmax_dense_launches", &softmax_dense_launches);
+  m.def("softmax_dense_max_c", &ps_softmax_dense_max_c);
   m.def("relu_forward", &relu_forward);
   m.def("relu_backward", &relu_backward);
   m.def("sigmoid_forward", &sigmoid_forward);

@@ -256,6 +256,34 @@ void ps_softmax_loss_fwd_bf16(const void*, const float*, void*, float*,
                               float*, int64_t, int, hipStream_t);
 void ps_softmax_loss_bwd_bf16(const void*, const float*, void*, int64_t, int,
                               float, hipStream_t);
+// loss[0] += partial[0 .. n), one block, in a fixed order (loss_sum_k)
+void ps_loss_sum(const float* partial, float* loss, int64_t n, hipStream_t);
+
+// softmax_dense.hip: per-position softmax loss over rows of C contiguous
+// logits (rows = N*H*W of a channels-last blob), labels[rows] fp32. Lane-group
+// kernels, plan in ps_softmax_dense_plan.h; they take what
+// ps_softmax_dense_ok() accepts and 16-byte aligned tensors, anything else
+// belongs on the wave-per-row kernels above.
+// fwd (x, labels, prob, loss, partial, rows, C, max_blocks): loss += mean of
+// -log p over the rows, by one atomicAdd per block, or with partial
+// (ps_softmax_dense_blocks() floats; required in deterministic mode) by one
+// ordered sum of the blocks' terms. max_blocks: cap of the grid, 0 = the
+// plan's own; the same value sizes partial.
+// bwd (prob, labels, dx, rows, C, w): dx = (prob - onehot) * w.
+int ps_softmax_dense_ok(int64_t rows, int64_t C, int itemsize);
+int ps_softmax_dense_max_c();
+int64_t ps_softmax_dense_blocks(int64_t rows, int C, int itemsize,
+                                int max_blocks);
+void ps_softmax_dense_fwd_f32(const float*, const float*, float*, float*,
+                              float*, int64_t, int, int, hipStream_t);
+void ps_softmax_dense_fwd_bf16(const void*, const float*, void*, float*,
+                               float*, int64_t, int, int, hipStream_t);
+void ps_softmax_dense_bwd_f32(const float*, const float*, float*, int64_t, int,
+                              float, hipStream_t);
+void ps_softmax_dense_bwd_bf16(const void*, const float*, void*, int64_t, int,
+                               float, hipStream_t);
+// host-side count of the launches above
+int64_t ps_softmax_dense_launches(int reset);
 
 // sgd.hip
 void ps_sgd_update(float*, const float*, float*, int64_t, float, float, float,

@@ -175,6 +175,9 @@ void ps_softmax_loss_fwd_bf16(const void* x, const float* labels, void* prob,
   softmax_loss_fwd<__bf16>((const __bf16*)x, labels, (__bf16*)prob, loss_out,
                            row_loss, rows, C, s);
 }
+void ps_loss_sum(const float* partial, float* loss, int64_t n, hipStream_t s) {
+  loss_sum_k<<<1, 256, 0, s>>>(partial, loss, n);
+}
 void ps_softmax_loss_bwd_f32(const float* prob, const float* labels, float* dx,
                              int64_t rows, int C, float w, hipStream_t s) {
   softmax_loss_bwd_k<float, float><<<ew_grid(rows * C), 256, 0, s>>>(

@@ -887,8 +887,70 @@ def softmax_backward(y: torch.Tensor, dy: torch.Tensor) -> torch.Tensor:
     return (dy - dot) * y
 
 
-def softmax_loss_forward(logits: torch.Tensor, labels: torch.Tensor):
-    """Returns (mean NLL over batch as 0-d tensor, probs)."""
+# Dense (per-position) softmax loss: 4-D logits (N, C, H, W) with one label
+# per (n, h, w), softmax over C at every position, loss and gradient divided
+# by N*H*W (softmax_loss_layer.cpp:46-55, :76-85). On the GPU the lane-group
+# kernels of softmax_dense.hip run it where their plan takes C; the switch
+# below puts it on the wave-per-row kernels with rows = N*H*W instead.
+_softmax_dense = os.environ.get("PS_SOFTMAX_DENSE", "1") not in ("", "0")
+
+
+def set_softmax_dense(on: bool) -> None:
+    """Toggle the lane-group kernels of the dense softmax loss (default on;
+    the environment variable PS_SOFTMAX_DENSE=0/1 sets it at import). Off
+    runs the dense loss on the wave-per-row kernels, for A/B runs."""
+    global _softmax_dense
+    _softmax_dense = bool(on)
+
+
+def softmax_dense() -> bool:
+    return _softmax_dense
+
+
+def softmax_dense_launches(reset: bool = False) -> int:
+    """Launches so far of the lane-group kernels (a host-side counter)."""
+    if not ext_available():
+        return 0
+    return int(_ext().softmax_dense_launches(bool(reset)))
+
+
+# SD_MAX_C of ps_softmax_dense_plan.h (64 lanes x 3 elements), for hosts
+# without the extension; tests/test_softmax_dense_cpu.py holds the two equal
+SOFTMAX_DENSE_MAX_C = 192
+
+
+def softmax_dense_max_c() -> int:
+    """Largest C the lane-group kernels take; above it the dense loss runs
+    on the wave-per-row kernels whatever the switch says."""
+    if not ext_available():
+        return SOFTMAX_DENSE_MAX_C
+    return int(_ext().softmax_dense_max_c())
+
+
+def _dense_labels(t: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:
+    n, c, h, w = t.shape
+    if labels.numel() != n * h * w:
+        raise ValueError(
+            f"softmax loss: logits of shape {tuple(t.shape)} need "
+            f"N*H*W = {n * h * w} labels, got shape {tuple(labels.shape)}")
+    return labels.reshape(n, 1, h, w)
+
+
+def softmax_loss_forward(logits: torch.Tensor, labels: torch.Tensor,
+                         dense_max_blocks: int = 0):
+    """Returns (mean NLL as 0-d tensor, probs). 2-D logits (N, C): one label
+    per row, mean over N. 4-D logits (N, C, H, W): one label per position,
+    mean over N*H*W, probs channels-last on the GPU. dense_max_blocks caps
+    the grid of the lane-group forward (0 = the plan's own cap); tests lower
+    it so that the blocks of a small tensor walk several tiles."""
+    if logits.dim() == 4:
+        idx = _dense_labels(logits, labels)
+        if logits.is_cuda:
+            return _ext().softmax_loss_dense_forward(
+                logits, labels, _softmax_dense, int(dense_max_blocks))
+        idx = idx.long().clamp(0, logits.shape[1] - 1)
+        logp = F.log_softmax(logits, dim=1)
+        return -logp.gather(1, idx).sum() / idx.numel(), logp.exp()
     if logits.is_cuda:
         return _ext().softmax_loss_forward(logits, labels)
     prob = F.softmax(logits, dim=1)
@@ -900,6 +962,16 @@ def softmax_loss_forward(logits: torch.Tensor, labels: torch.Tensor):
 
 def softmax_loss_backward(prob: torch.Tensor, labels: torch.Tensor,
                           loss_weight: float) -> torch.Tensor:
+    """(prob - onehot(label)) * loss_weight / rows, rows = N (2-D) or N*H*W
+    (4-D, see softmax_loss_forward)."""
+    if prob.dim() == 4:
+        idx = _dense_labels(prob, labels)
+        if prob.is_cuda:
+            return _ext().softmax_loss_dense_backward(
+                prob, labels, float(loss_weight), _softmax_dense)
+        # a label outside [0, C) matches no channel, as on the GPU
+        onehot = idx.long() == torch.arange(prob.shape[1]).view(1, -1, 1, 1)
+        return (prob - onehot.to(prob.dtype)) * (loss_weight / idx.numel())
     if prob.is_cuda:
         return _ext().softmax_loss_backward(prob, labels, loss_weight)
     n = prob.shape[0]

@@ -26,6 +26,7 @@ sources = [
         "lrn_within.hip",
         "mvn.hip",
         "softmax.hip",
+        "softmax_dense.hip",
         "sgd.hip",
         "im2col.hip",
         "conv_rowfused.hip",
