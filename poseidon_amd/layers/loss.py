@@ -71,10 +71,18 @@ class SoftmaxWithLossLayer(LossLayer):
     spatial_dim = H*W): one label per (n, h, w) of an (N, C, H, W) bottom is
     the dense loss -- softmax over C at every position, normalised by N*H*W,
     the 4-D tensor handed to the op as it lies; one label per image keeps
-    the classifier reading of the bottom as (N, C*H*W)."""
+    the classifier reading of the bottom as (N, C*H*W).
+
+    A second top is the softmax output, shaped like bottom[0] and sharing
+    the layer's cached prob (softmax_loss_layer.cpp:31-33, :56-57); its diff
+    is ignored going back, as there."""
+
+    max_top = 2
 
     def reshape(self, bottom, top) -> None:
         super().reshape(bottom, top)
+        if len(top) > 1:
+            top[1].reshape(bottom[0].shape)
         b, n = bottom[0], bottom[1].count
         dense = b.num * b.height * b.width
         self._dense = b.height * b.width > 1 and n == dense
@@ -97,6 +105,8 @@ class SoftmaxWithLossLayer(LossLayer):
         self._labels = labels
         if top:
             top[0].data = loss.reshape(())
+        if len(top) > 1:
+            top[1].data = prob.view(b.shape)  # shared, not copied
 
     def backward(self, top, propagate_down, bottom) -> None:
         if len(propagate_down) > 1 and propagate_down[1]:
@@ -289,10 +299,25 @@ class AccuracyLayer(Layer):
         self.top_k = int(ap.top_k) if ap is not None else 1
 
     def reshape(self, bottom, top) -> None:
+        """One label per (n, h, w) scores every position over its channels;
+        one per image keeps the classifier reading of the bottom as
+        (N, C*H*W), as in SOFTMAX_LOSS."""
         top[0].reshape(())
+        b = bottom[0]
+        self._dense = ops.accuracy_label_mode(
+            (b.num, b.channels, b.height, b.width), bottom[1].count,
+            f"ACCURACY {self.name!r}")
+        classes = b.channels if self._dense else b.count // max(b.num, 1)
+        if self.top_k > classes:  # accuracy_layer.cpp:26
+            raise ValueError(
+                f"ACCURACY {self.name!r}: top_k = {self.top_k} is more than "
+                f"the {classes} classes of a bottom of shape {b.shape}")
 
     def forward(self, bottom, top) -> None:
-        top[0].data = ops.accuracy(bottom[0].data, bottom[1].data,
+        b = bottom[0]
+        pred = b.data.view(b.num, b.channels, b.height, b.width) \
+            if self._dense else b.data
+        top[0].data = ops.accuracy(pred, bottom[1].data,
                                    self.top_k).reshape(())
 
     def backward(self, top, propagate_down, bottom) -> None:

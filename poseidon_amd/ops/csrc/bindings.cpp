@@ -1383,8 +1383,33 @@ Tensor empty_like_rows(const Tensor& tc) {
                                       : at::MemoryFormat::Preserve);
 }
 
-Tensor softmax_forward(const Tensor& x) {
+// A 4-D blob with more than one position whose rows (N*H*W of C channels)
+// the lane-group kernels take: softmax_heads.hip serves it, anything else
+// stays on the wave-per-row kernels.
+bool softmax_dense_rows(const Tensor& t, bool lane_groups) {
+  return lane_groups && t.dim() == 4 && t.size(2) * t.size(3) > 1 &&
+         t.numel() > 0 &&
+         ps_softmax_dense_ok(t.numel() / t.size(1), t.size(1),
+                             (int)t.element_size()) != 0;
+}
+
+// channels-last and 16-byte aligned, as the tile copies want
+Tensor cl4_aligned(const Tensor& t) {
+  Tensor tc = cl4(t);
+  if ((uintptr_t)tc.data_ptr() & 15)  // an offset view
+    tc = tc.clone(at::MemoryFormat::ChannelsLast);
+  return tc;
+}
+
+Tensor softmax_forward(const Tensor& x, bool lane_groups) {
   check_float_like(x, "x");
+  if (softmax_dense_rows(x, lane_groups)) {
+    Tensor xc = cl4_aligned(x);
+    Tensor y = empty_cl(xc.sizes(), xc.options());
+    PS_CALL(softmax_heads_fwd, is_bf16(xc), P(xc), P(y),
+            xc.numel() / xc.size(1), (int)xc.size(1), stream());
+    return y;
+  }
   int64_t rows;
   int C;
   Tensor xc = as_rows(x, &rows, &C);
@@ -1393,7 +1418,19 @@ Tensor softmax_forward(const Tensor& x) {
   return y;
 }
 
-Tensor softmax_backward(const Tensor& y, const Tensor& dy) {
+Tensor softmax_backward(const Tensor& y, const Tensor& dy, bool lane_groups) {
+  if (softmax_dense_rows(y, lane_groups)) {
+    check_float_like(y, "y");
+    TORCH_CHECK(dy.is_cuda() && dy.sizes() == y.sizes() &&
+                    dy.scalar_type() == y.scalar_type(),
+                "softmax backward: dy of shape ", dy.sizes(),
+                " does not match y of shape ", y.sizes());
+    Tensor yc = cl4_aligned(y), dyc = cl4_aligned(dy);
+    Tensor dx = empty_cl(yc.sizes(), yc.options());
+    PS_CALL(softmax_heads_bwd, is_bf16(yc), P(yc), P(dyc), P(dx),
+            yc.numel() / yc.size(1), (int)yc.size(1), stream());
+    return dx;
+  }
   int64_t rows;
   int C;
   Tensor yc = as_rows(y, &rows, &C);
@@ -1459,10 +1496,8 @@ DenseLossArgs dense_loss_args(const Tensor& t, const Tensor& labels,
               labels.sizes());
   TORCH_CHECK(rows >= 1 && t.size(1) >= 1 && t.size(1) < (1 << 30),
               "softmax loss (dense): empty or oversized ", name);
-  Tensor tc = cl4(t);
-  if ((uintptr_t)tc.data_ptr() & 15)  // an offset view: the vector loads
-    tc = tc.clone(at::MemoryFormat::ChannelsLast);  // want 16 bytes
-  return {tc, labels.contiguous().to(at::kFloat), rows, (int)t.size(1),
+  return {cl4_aligned(t), labels.contiguous().to(at::kFloat), rows,
+          (int)t.size(1),
           lane_groups &&
               ps_softmax_dense_ok(rows, t.size(1), (int)t.element_size()) != 0};
 }
@@ -1515,6 +1550,24 @@ Tensor softmax_loss_dense_backward(const Tensor& prob, const Tensor& labels,
 
 int64_t softmax_dense_launches(bool reset) {
   return ps_softmax_dense_launches(reset ? 1 : 0);
+}
+
+// Per-position top-k accuracy of an (N, C, H, W) prediction, one label per
+// (n, h, w): the fraction of positions whose label has fewer than top_k
+// channels ranked ahead of it, a 0-d fp32 tensor that never visits the host.
+// lane_groups as for the dense loss.
+Tensor accuracy_dense(const Tensor& pred, const Tensor& labels, int64_t top_k,
+                      bool lane_groups) {
+  const DenseLossArgs a = dense_loss_args(pred, labels, lane_groups, "pred");
+  TORCH_CHECK(top_k >= 1 && top_k <= a.C, "accuracy: top_k = ", top_k,
+              " needs 1 <= top_k <= C = ", a.C);
+  TORCH_CHECK(a.rows < (1LL << 31), "accuracy: too many positions");
+  Tensor count = at::zeros({}, a.t.options().dtype(at::kInt));
+  Tensor acc = at::empty({}, a.t.options().dtype(at::kFloat));
+  PS_CALL(accuracy_rows, is_bf16(a.t), P(a.t), a.labels.data_ptr<float>(),
+          count.data_ptr<int>(), acc.data_ptr<float>(), a.rows, a.C,
+          (int)top_k, a.lane_groups ? 1 : 0, stream());
+  return acc;
 }
 
 // ---------------------------------------------------------------------------
@@ -2164,6 +2217,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("softmax_loss_dense_forward", &softmax_loss_dense_forward);
   m.def("softmax_loss_dense_backward", &softmax_loss_dense_backward);
   m.def("softmax_dense_launches", &softmax_dense_launches);
+  m.def("accuracy_dense", &accuracy_dense);
   m.def("softmax_dense_max_c", &ps_softmax_dense_max_c);
   m.def("relu_forward", &relu_forward);
   m.def("relu_backward", &relu_backward);

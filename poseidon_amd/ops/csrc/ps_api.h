@@ -282,8 +282,33 @@ void ps_softmax_dense_bwd_f32(const float*, const float*, float*, int64_t, int,
                               float, hipStream_t);
 void ps_softmax_dense_bwd_bf16(const void*, const float*, void*, int64_t, int,
                                float, hipStream_t);
-// host-side count of the launches above
+// host-side count of the launches above and of softmax_heads.hip's
+// lane-group kernels, which add theirs with ps_softmax_dense_count_launch()
 int64_t ps_softmax_dense_launches(int reset);
+void ps_softmax_dense_count_launch();
+
+// softmax_heads.hip: the plain softmax over rows of C contiguous elements
+// (rows = N*H*W of a channels-last blob) on lane-group kernels, for what
+// ps_softmax_dense_ok() accepts and 16-byte aligned tensors.
+// fwd (x, y, rows, C): y = softmax(x) per row.
+// bwd (y, dy, dx, rows, C): dx = (dy - sum_c dy * y) * y per row.
+void ps_softmax_heads_fwd_f32(const float*, float*, int64_t, int, hipStream_t);
+void ps_softmax_heads_fwd_bf16(const void*, void*, int64_t, int, hipStream_t);
+void ps_softmax_heads_bwd_f32(const float*, const float*, float*, int64_t, int,
+                              hipStream_t);
+void ps_softmax_heads_bwd_bf16(const void*, const void*, void*, int64_t, int,
+                               hipStream_t);
+// (x, labels, count, acc, rows, C, top_k, lane_groups): top-k accuracy over
+// the rows by rank counting, labels[rows] fp32. count (pre-zeroed int32) +=
+// the rows whose label has fewer than top_k elements ahead of it (greater, or
+// equal with a higher index); a label outside [0, C) or a NaN at the label
+// is a miss. acc[0] = count / rows, on the device. lane_groups: the
+// lane-group kernel where ps_softmax_dense_ok() holds (x then 16-byte
+// aligned), else and above SD_MAX_C one wave per row. 1 <= top_k <= C.
+void ps_accuracy_rows_f32(const float*, const float*, int*, float*, int64_t,
+                          int, int, int, hipStream_t);
+void ps_accuracy_rows_bf16(const void*, const float*, int*, float*, int64_t,
+                           int, int, int, hipStream_t);
 
 // sgd.hip
 void ps_sgd_update(float*, const float*, float*, int64_t, float, float, float,

@@ -101,4 +101,41 @@ inline SoftmaxDensePlan sd_plan(int64_t rows, int C, int itemsize,
   return p;
 }
 
+// The plan of a kernel that keeps `streams` tiles of the same TR rows in LDS
+// at once (softmax_heads.hip: the softmax backward stages y and dy, 2; the
+// softmax forward and the accuracy kernel stage one). The tiles lie one
+// behind the other, each sd_tile_bytes() long, the room of TR labels behind
+// the last; TR follows sd_plan's unit rule and is sized so that all of it
+// fits SD_TILE_BYTES. streams == 1 is sd_plan.
+//
+// Two tiles of pitch C, reasoned as above and as little measured: a lane
+// reads y[r][c] and dy[r][c] with two instructions, so the tiles never meet
+// in one access, and the second tile is the first one moved by
+// sd_tile_bytes(), the same number of banks for every lane -- a rotation of
+// the bank pattern, which conflicts exactly where the single tile does. The
+// C == 2 G flip therefore serves both reads, and the dx store, which goes to
+// the address its lane read dy from, repeats the dy read's pattern. What two
+// tiles change is TR (about half), not the access.
+inline SoftmaxDensePlan sd_plan_streams(int64_t rows, int C, int itemsize,
+                                        int streams) {
+  SoftmaxDensePlan p = sd_plan(rows, C, itemsize, 0);
+  if (p.G == 0 || streams <= 1) return p;
+  const int vn = 16 / itemsize;
+  const int rb = SD_THREADS / p.G;
+  const int unit = rb > vn ? rb : vn;
+  int64_t k = SD_TILE_BYTES /
+              ((int64_t)unit * ((int64_t)streams * C * itemsize + 4));
+  const int64_t fill = rows / (unit * SD_FILL_BLOCKS);
+  if (k > fill) k = fill;
+  if (k < 1) k = 1;
+  p.TR = (int)(k * unit);
+  p.tiles = (rows + p.TR - 1) / p.TR;
+  p.blocks = p.tiles < SD_MAX_BLOCKS ? p.tiles : SD_MAX_BLOCKS;
+  p.lds = (size_t)streams * sd_tile_bytes(p.TR, C, itemsize) +
+          4 * (size_t)p.TR;
+  // one unit of rows always fits for streams <= 2; more may not
+  if (p.lds > (size_t)SD_TILE_BYTES) p = SoftmaxDensePlan{};
+  return p;
+}
+
 }  // namespace ps

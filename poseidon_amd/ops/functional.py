@@ -874,15 +874,18 @@ def relu_backward_bias(x, dy, db):
 # ---------------------------------------------------------------------------
 
 def softmax_forward(x: torch.Tensor) -> torch.Tensor:
-    """Channel softmax per spatial position (softmax_layer.cu)."""
+    """Channel softmax per spatial position (softmax_layer.cu). On the GPU a
+    4-D blob with H*W > 1 and C within softmax_dense_max_c() runs on the
+    lane-group kernels of softmax_heads.hip, output channels-last, unless
+    set_softmax_dense(False); everything else one wave per row."""
     if x.is_cuda:
-        return _ext().softmax_forward(x)
+        return _ext().softmax_forward(x, _softmax_dense)
     return F.softmax(x, dim=1)
 
 
 def softmax_backward(y: torch.Tensor, dy: torch.Tensor) -> torch.Tensor:
     if y.is_cuda:
-        return _ext().softmax_backward(y, dy)
+        return _ext().softmax_backward(y, dy, _softmax_dense)
     dot = (dy * y).sum(dim=1, keepdim=True)
     return (dy - dot) * y
 
@@ -896,9 +899,10 @@ _softmax_dense = os.environ.get("PS_SOFTMAX_DENSE", "1") not in ("", "0")
 
 
 def set_softmax_dense(on: bool) -> None:
-    """Toggle the lane-group kernels of the dense softmax loss (default on;
-    the environment variable PS_SOFTMAX_DENSE=0/1 sets it at import). Off
-    runs the dense loss on the wave-per-row kernels, for A/B runs."""
+    """Toggle the lane-group kernels of the dense softmax loss, the 4-D
+    softmax and the per-position accuracy (default on; the environment
+    variable PS_SOFTMAX_DENSE=0/1 sets it at import). Off runs all three on
+    wave-per-row kernels, for A/B runs."""
     global _softmax_dense
     _softmax_dense = bool(on)
 
@@ -1448,7 +1452,52 @@ def data_transform(raw: torch.Tensor, params: torch.Tensor,
 # Metrics
 # ---------------------------------------------------------------------------
 
+def accuracy_label_mode(shape, n_labels: int, who: str = "accuracy") -> bool:
+    """True: one label per (n, h, w) of a 4-D prediction with H*W > 1, the
+    per-position metric; False: one per image. Any other count raises."""
+    n = int(shape[0])
+    dense = n * int(shape[2]) * int(shape[3]) if len(shape) == 4 else n
+    if n_labels == n:
+        return False
+    if n_labels != dense:
+        raise ValueError(
+            f"{who}: prediction of shape {tuple(shape)} takes {n} labels "
+            "(one per image)"
+            + (f" or {dense} (one per position)" if dense != n else "")
+            + f", got {n_labels}")
+    return True
+
+
+def _accuracy_dense(pred: torch.Tensor, labels: torch.Tensor,
+                    top_k: int) -> torch.Tensor:
+    """The per-position metric by rank counting: a position is right iff fewer
+    than top_k channels rank ahead of its label's -- greater, or equal with a
+    higher index, the order of the reference's partial_sort over (value,
+    index) pairs (accuracy_layer.cpp:51-58). A label outside [0, C) or a NaN
+    at the label is wrong."""
+    n, c, h, w = pred.shape
+    if not 1 <= top_k <= c:
+        raise ValueError(f"accuracy: top_k = {top_k} needs 1 <= top_k <= "
+                         f"C = {c}")
+    if pred.is_cuda:
+        return _ext().accuracy_dense(pred, labels, int(top_k), _softmax_dense)
+    x = pred.permute(0, 2, 3, 1).reshape(n * h * w, c)
+    lbl = labels.reshape(-1).long()
+    ok = (lbl >= 0) & (lbl < c)
+    lbl = lbl.clamp(0, c - 1).view(-1, 1)
+    v = x.gather(1, lbl)
+    ahead = (x > v) | ((x == v) & (torch.arange(c).view(1, -1) > lbl))
+    hit = ok & (v == v).view(-1) & (ahead.sum(dim=1) < top_k)
+    return hit.to(torch.float32).sum() / (n * h * w)
+
+
 def accuracy(pred: torch.Tensor, labels: torch.Tensor, top_k: int = 1) -> torch.Tensor:
+    """Top-k accuracy as a 0-d fp32 tensor. labels.numel() == N: one label
+    per image over the flattened prediction. 4-D pred with H*W > 1 and
+    labels.numel() == N*H*W: one label per position, top-k over the channels
+    of each; on the GPU softmax_heads.hip's rank-count kernel."""
+    if accuracy_label_mode(pred.shape, labels.numel()):
+        return _accuracy_dense(pred, labels, top_k)
     n = pred.shape[0]
     flat = pred.reshape(n, -1)
     if top_k == 1:

@@ -27,6 +27,7 @@ sources = [
         "mvn.hip",
         "softmax.hip",
         "softmax_dense.hip",
+        "softmax_heads.hip",
         "sgd.hip",
         "im2col.hip",
         "conv_rowfused.hip",
